@@ -1,7 +1,7 @@
 """Throughput benchmark of the Siamese U-Net training step on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config baseline_siamese] [--batch B]
-                    [--math h2|x3|x5|bf16|f32]
+                    [--math h2|x3|x5|bf16|f32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 One step = zero_grad -> SiameseUNet forward (HIP) -> power_jaccard_loss -> backward (HIP) -> AdamW step,
@@ -14,7 +14,13 @@ three fp16 MFMA products, fp32 accumulation; fp32-class results), MODEL.PRECISIO
 it (x3: exact three-term bf16 split, six products; x5: x3 less one product; f32: fp32 MFMA).  `dtype` names the
 arithmetic: "f32 (h2 split-fp16)" for the default.
 
-Measurement extras (rank 0, after the timed region):
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints the line (metric, value,
+ms_per_step, step_roofline: figures of the timed steps alone).  `--dump-outputs DIR` writes what the last timed step
+returned and left behind as DIR/<name>.npy (float32): the loss, the logits and a fixed seeded sample of the updated
+parameters; the inputs and the initial weights are seeded, so two builds run with the same arguments compare output
+for output.  Everything below takes runs of its own and is measured only with `--full`.
+
+Measurement extras (`--full`; rank 0, after the timed region):
   roofline      the MFMA conv kernels (every conv launch of one step) bracketed by HIP events on the launch
                 stream: algorithmic conv FLOPs per step / summed kernel time.  The peak is each launch's own
                 matrix-core ceiling (the library reports every launch's arithmetic: scd_igemm_arith /
@@ -310,6 +316,46 @@ def live_traffic(args, batch: int, size: int, timeout_s: int = 180):
                       "included, MI355X_MICROARCH.md HBM)"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all of --dump-outputs stays well under 64 MB
+DUMP_PARAM_SAMPLE = 4096      # elements kept per parameter tensor
+DUMP_SEED = 20240229
+
+
+def _named_outputs(out):
+    """The forward's return value as (name, tensor) pairs: one tensor, or a tuple / list / dict of them."""
+    if torch.is_tensor(out):
+        return [('logits', out)]
+    if isinstance(out, dict):
+        return [(f'logits_{k}', v) for k, v in out.items() if torch.is_tensor(v)]
+    return [(f'logits_{i}', v) for i, v in enumerate(out) if torch.is_tensor(v)]
+
+
+def dump_outputs(path: str, loss, out, net):
+    """Write the last timed step's results as <path>/<name>.npy (float32): loss, the forward's outputs, and
+    DUMP_PARAM_SAMPLE seeded elements of every updated parameter (params_sample, in named_parameters order).  An
+    output larger than its share of DUMP_BUDGET_BYTES is stored as a seeded sample of its elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.RandomState(DUMP_SEED)
+    np.save(os.path.join(path, 'loss.npy'), loss.detach().float().cpu().numpy().reshape(1))
+    outs = _named_outputs(out)
+    share = DUMP_BUDGET_BYTES // (4 * max(1, len(outs)))  # elements per output
+    for name, t in outs:
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, f'{name}.npy'), a)
+    module = net.module if hasattr(net, 'module') else net
+    parts = []
+    for _, p in module.named_parameters():
+        a = p.detach().float().cpu().numpy().reshape(-1)
+        if a.size > DUMP_PARAM_SAMPLE:
+            a = a[np.sort(rng.choice(a.size, DUMP_PARAM_SAMPLE, replace=False))]
+        parts.append(a)
+    np.save(os.path.join(path, 'params_sample.npy'), np.concatenate(parts))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -318,6 +364,11 @@ def main():
     ap.add_argument('--config', default='baseline_siamese')
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (default: config TRAINER.BATCH_SIZE)')
     ap.add_argument('--size', type=int, default=None)
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the last timed step\'s loss, logits and a seeded parameter sample as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure the extras (roofline, traffic, cpu_baseline, distributed); '
+                         'the --no-* switches below trim them')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--no-traffic', action='store_true',
@@ -328,6 +379,10 @@ def main():
     ap.add_argument('--storage', default=None, choices=['fp32', 'bf16'],
                     help='activation / gradient storage (default: engine.act_storage_for: bf16 for the bf16 arithmetic)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:  # a plain run measures the headline figure only
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_traffic = True
 
     rank, local_rank, world = parallel.init_distributed()
     dev = torch.device('cuda', parallel.device_index(local_rank))
@@ -359,28 +414,37 @@ def main():
     b = datasets.synthetic_batch(cfg, batch, dev, gen, size)
     hip.ensure_device(b['x_t1'])
 
-    def step():
+    kept = []  # the forward's outputs of the last timed step, kept only for --dump-outputs
+
+    def step(keep: bool = False):
         opt.zero_grad(set_to_none=True)
-        loss = trainers.step_loss(cfg, net(b['x_t1'], b['x_t2']), b, net)  # the config's trainer recipe
+        out = net(b['x_t1'], b['x_t2'])
+        if keep:
+            kept.append(out)
+        loss = trainers.step_loss(cfg, out, b, net)  # the config's trainer recipe
         loss.backward()
         opt.step()
         return loss
 
+    loss = None
     for _ in range(args.warmup):
         loss = step()
     torch.cuda.synchronize()
-    first_loss = float(loss.item())
+    first_loss = float(loss.item()) if loss is not None else None  # --warmup 0: no loss before the timed steps
 
+    dump = bool(args.dump_outputs) and rank == 0
     parallel.barrier(dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(dump and i == args.steps - 1)
     torch.cuda.synchronize()
     parallel.barrier(dev)
     dt_local = time.perf_counter() - t0
     dt = parallel.allreduce_max(dt_local, dev)
     last_loss = float(loss.item())
+    if dump:  # before the extras run further steps
+        dump_outputs(args.dump_outputs, loss, kept.pop(), net)
 
     value = batch * world * args.steps / dt
     ms = 1000.0 * dt / args.steps
@@ -403,7 +467,7 @@ def main():
                                f"conv math {math}, {storage} activation storage, train step incl. AdamW",
                    "global_batch": batch * world, "tile": size, "parallelism": f"dp{world}",
                    "topology": list(cfg.MODEL.TOPOLOGY)},
-        "loss_first_last": [round(first_loss, 6), round(last_loss, 6)],
+        "loss_first_last": [None if first_loss is None else round(first_loss, 6), round(last_loss, 6)],
     }
     if cfg.MODEL.TYPE == 'siameseunet':  # SURVEY 8(d) formula (273.3 GF/pair at 256^2, 5-ch)
         dpeak = PEAKS[math]
@@ -475,7 +539,7 @@ def main():
         if classes:
             dom = max(classes, key=lambda k: classes[k]["ms_per_step"])
             result["roofline"]["dominant_kernel"] = dict(classes[dom], **{"class": dom})
-    if parallel.is_distributed():  # every rank: the probe steps and the report run collectives
+    if args.full and parallel.is_distributed():  # every rank: the probe steps and the report run collectives
         probe = parallel.ExposedAllreduceProbe(net.module, dev)
         exposed = []
         for _ in range(3):

@@ -6,5 +6,5 @@ out=${1:-gpurun_out/round}
 mkdir -p "$out"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > "$out/pytest.log" 2>&1
 timeout -k 10 180 python -u __graft_entry__.py smoke > "$out/smoke.log" 2>&1
-timeout -k 10 300 python -u bench.py > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 300 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 cat "$out/bench.json"

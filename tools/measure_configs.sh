@@ -5,7 +5,7 @@ set -e
 out=${1:-gpurun_out/configs.jsonl}
 mkdir -p "$(dirname "$out")"
 : > "$out"
-run() { timeout -k 10 240 python -u bench.py --no-cpu-baseline "$@" >> "$out" 2>> "$out.err"; }
+run() { timeout -k 10 240 python -u bench.py --full --no-cpu-baseline "$@" >> "$out" 2>> "$out.err"; }
 run --config baseline_siamese
 run --config baseline_siamese --batch 64
 run --config baseline_siamese --math x3

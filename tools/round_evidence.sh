@@ -5,7 +5,7 @@
 set -e
 out=${1:-gpurun_out/ev}
 mkdir -p "$out"
-timeout -k 10 300 python -u bench.py > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 300 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 bash tools/profile_round.sh "$out/prof"
 python tools/pmc_traffic.py "$out/prof" --steps 4 --summaries "$out/r" > "$out/pmc_traffic.json"
 timeout -k 10 300 python -u tools/perf_conv.py --math h2 > "$out/perf_conv.txt" 2> "$out/perf_conv.err"
