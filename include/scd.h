@@ -152,7 +152,10 @@ enum scd_conv_math {
  *      scd_bn_relu_backward_pooled2 (a second, swapped skip gradient), scd_conv1x1_fwd_bn2 (two-source heads).
  *   8: scd_wgrad_t.rows_out / rows_out_bound appended (the halo weight grad forms and stores a plain BatchNorm
  *      backward's dY).
- *   9: scd_igemm_t.dst_bound_seed appended (a bound seeded with another buffer's bound inside the conv launch). */
+ *   9: scd_igemm_t.dst_bound_seed appended (a bound seeded with another buffer's bound inside the conv launch).
+ *      Still 9 (no layout or signature change): three tune selectors were withdrawn with their kernels, all measured
+ *      slower -- the late halo load (bit 27), the warp-specialized h2 tiles (bit 29) and the double-buffered h2
+ *      weight grad (bit 31). */
 #define SCD_ABI_VERSION 9
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
@@ -192,16 +195,14 @@ int scd_abi_version(void);
 #define SCD_TUNE_NO_WGRAD_H2      (1u << 24)  /* ConvTranspose weight grad on x3 instead of h2                    */
 #define SCD_TUNE_NO_HALO16_C16    (1u << 25)  /* input-layer forward on the per-tap x3 kernel                     */
 #define SCD_TUNE_NO_HALO          (1u << 26)  /* no halo kernels at all (per-tap kernels)                         */
-#define SCD_TUNE_HALO16_LATE_LOAD (1u << 27)  /* single-buffered halo16: next chunk's halo loaded at the last tap  */
+/* bit 27: reserved, must be 0 */
 #define SCD_TUNE_H2_TILE64_128    (1u << 28)  /* 64..127 outputs of 64-channel sources (h2, bf16 storage): 128 x 64
                                                  tiles instead of 256 x 64 (2x2 waves of 128 px x 32 ch)             */
-#define SCD_TUNE_HALO16_WS        (1u << 29)  /* h2 1 x N tiles as warp-specialized blocks: one producer wave stages
-                                                 the halo, the compute waves load only weights (128 px tiles)        */
+/* bit 29: reserved, must be 0 */
 #define SCD_TUNE_WGRAD16_REGSTAGE (1u << 30)  /* bf16-storage halo weight grad staged through registers, one patch in
                                                  flight, instead of the LDS-DMA ring (A/B; until ABI 8 this bit chose
                                                  persistent ConvT gather blocks, removed: measured slower)           */
-#define SCD_TUNE_WGRAD16_DB       (1u << 31)  /* h2 halo weight grad with two patch buffers, one barrier per patch and
-                                                 (128-row blocks) the two wave groups staggered                      */
+/* bit 31: reserved, must be 0 */
 /* dst[p*n + i] = bf16 bits of term p (h, m, l) of src[i]: the exact 3-way split used by SCD_MATH_X3.
  * n % 8 == 0, src and dst 16-byte aligned. */
 int scd_split_bf16x3(const float *src, int64_t n, uint16_t *dst, scd_stream_t stream);

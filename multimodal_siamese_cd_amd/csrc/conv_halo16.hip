@@ -324,9 +324,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void igemm_halo16_x3(I
     const int nsteps = cpk * a.ntaps;
     constexpr int T_STORE = 4;  // DB: tap at which the prefetched halo is written to the other buffer
     // single buffer: the tap at which the next chunk's halo loads are issued into registers (stored at the chunk end),
-    // 4 taps ahead so HBM latency hides behind 4 taps of MFMAs; SCD_TUNE_HALO16_LATE_LOAD: the last tap (A/B)
+    // 4 taps ahead so HBM latency hides behind 4 taps of MFMAs (convs of fewer than 5 taps: the last tap)
     // (WL: always 4 taps ahead; the launcher takes WL for 9-tap convs only)
-    const int t_load = !WL && ((a.tune & SCD_TUNE_HALO16_LATE_LOAD) || a.ntaps < 5) ? a.ntaps - 1 : a.ntaps - 5;
+    const int t_load = !WL && a.ntaps < 5 ? a.ntaps - 1 : a.ntaps - 5;
     u32x4 wq[WP][TN];
     if constexpr (WL) {
         issue_W(0);
@@ -689,342 +689,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void igemm_halo16_x3(I
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Warp-specialized h2 halo forward / data grad (SCD_TUNE_HALO16_WS): WAVES_N compute waves of 128 px x 32 ch (the
-// 1 x N wave tiles of igemm_halo16_x3) plus one producer wave per block.  The producer alone loads each 32-channel
-// chunk's halo, applies the input transform, splits it into the fp16 h / pre-scaled m planes and writes them into the
-// other of two LDS buffers while the compute waves run the current chunk.  The compute waves' only vector-memory stream
-// is their own weight fragments, one k-step ahead: vmcnt retires in order per wave, so in igemm_halo16_x3 every weight
-// wait also drained the next chunk's halo loads (about one k-step of MFMAs to hide an HBM latency); here those loads
-// belong to a wave that waits for nothing else.  One barrier per chunk.  Same products, reduction order and epilogue as
-// igemm_halo16_x3<..., NP = 4> (bit-identical outputs and records).
-// ------------------------------------------------------------------------------------------------
-template <int WAVES_N, int TM, int TN, int TW, int OCC, bool IN_BN>
-__global__ __launch_bounds__(64 * (WAVES_N + 1), OCC) void igemm_halo16_ws(IgemmArgs a) {
-    constexpr int NT = 64 * (WAVES_N + 1);
-    constexpr int WPX = TM * 16, WCH = TN * 16;
-    constexpr int BM = WPX, BN = WAVES_N * WCH;
-    constexpr int TR = BM / TW;
-    constexpr int HWD = TW + 2;
-    constexpr int HR = (TR + 2) * HWD;
-    constexpr int A_CH = HR * 8;               // 16-byte (4-channel) pieces of one 32-channel chunk
-    constexpr int P_PER = (A_CH + 63) / 64;    // per producer lane
-    constexpr int PA = HR * 64;                // one plane
-    constexpr int BUF = 2 * PA;                // h and m planes
-    constexpr int RG = TM >= 8 ? TM / 4 : 1;   // reduction groups per wave (igemm_halo16_x3's order)
-    constexpr int TMG = TM / RG;
-    constexpr int WME = RG;                    // reduction rows of the block (one wave row)
-    constexpr int RED = 2 * WME * BN * 4;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUF > RED ? 2 * BUF : RED];
-    float xs = 1.f, xs_inv = 1.f;
-    h2_scale(*a.src_bound, xs, xs_inv);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: the role branch is scalar
-    const bool producer = wid == WAVES_N;
-    const int wn = producer ? 0 : wid;
-    const int g = lane >> 4, l16 = lane & 15;
-    int mt, nt;
-    if (a.remap == 2) {
-        const uint32_t L = xcd_swizzle(blockIdx.x, uint32_t(a.grid_m * a.grid_n));
-        nt = int(L / uint32_t(a.grid_m));
-        mt = int(L - uint32_t(nt) * uint32_t(a.grid_m));
-    } else if (a.remap) {
-        const uint32_t L = xcd_swizzle(blockIdx.x, uint32_t(a.grid_m * a.grid_n));
-        mt = int(L / uint32_t(a.grid_n));
-        nt = int(L - uint32_t(mt) * uint32_t(a.grid_n));
-    } else {
-        mt = int(blockIdx.x % uint32_t(a.grid_m));
-        nt = int(blockIdx.x / uint32_t(a.grid_m));
-    }
-    const int tiles_x = a.wo / TW, tiles_y = a.ho / TR;
-    const int img = mt / (tiles_x * tiles_y);
-    const int trem = mt - img * tiles_x * tiles_y;
-    const int ty = trem / tiles_x;
-    const int y0 = ty * TR, x0 = (trem - ty * tiles_x) * TW;
-    const int n0 = nt * BN;
-    const int cpk = a.c / 32;
-    const int nsteps = cpk * a.ntaps;
-
-    f32x4 acc[TN][TM];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (producer) {
-        // ---- the producer: halo of chunk cc + 1 while the compute waves run chunk cc
-        auto soff = [](int row, int col) { return row * 64 + ((((col >> 1) ^ (row >> 1)) & 3) << 4) + ((col & 1) << 3); };
-        const int col = lane & 7;  // the channel piece of every piece of this lane (e = lane + 64 i)
-        uint32_t p_boff[P_PER];
-        int p_off[P_PER];
-#pragma unroll
-        for (int i = 0; i < P_PER; ++i) {
-            const int e = lane + i * 64;
-            const bool in = e < A_CH;
-            const int hp = in ? (e >> 3) : 0;
-            const int hy = hp / HWD, hx = hp - (hp / HWD) * HWD;
-            const int sy = y0 - 1 + hy, sx = x0 - 1 + hx;
-            const bool ok = in && unsigned(sy) < unsigned(a.hs) && unsigned(sx) < unsigned(a.ws);
-            p_boff[i] = ok ? uint32_t(((img * a.hs + sy) * a.ws + sx) * a.ldc_s + col * 4) * 4u : kOOB;
-            p_off[i] = in ? soff(hp, col) : -1;
-        }
-        const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(a.src, a.src_bytes);
-        f32x4 ra[P_PER];
-        f32x4 in_sc, in_sh;
-        auto pload = [&](int cc) {
-#pragma unroll
-            for (int i = 0; i < P_PER; ++i) ra[i] = bload4(rs_src, p_boff[i] == kOOB ? kOOB : p_boff[i] + cc * 128u);
-            if constexpr (IN_BN) {
-                const int ch = (img / a.in_seg_imgs) * a.c + cc * 32 + col * 4;
-                in_sc = gload4(a.in_scale + ch) * xs;  // fma(y, sc s, sh s) == s fma(y, sc, sh): s a power of two
-                in_sh = gload4(a.in_shift + ch) * xs;
-            }
-        };
-        auto pstore = [&](int buf) {
-            unsigned char *const sb = smem + buf * BUF;
-#pragma unroll
-            for (int i = 0; i < P_PER; ++i)
-                if ((A_CH % 64 == 0) || p_off[i] >= 0) {
-                    f32x4 x = ra[i];
-                    if constexpr (IN_BN) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            x[q] = p_boff[i] == kOOB ? 0.f : fmaxf(fmaf(x[q], in_sc[q], in_sh[q]), 0.f);
-                    } else {
-                        x *= xs;
-                    }
-                    u32x2 h, m;
-                    split2h_pre(x, h, m);
-                    *reinterpret_cast<u32x2 *>(sb + p_off[i]) = h;
-                    *reinterpret_cast<u32x2 *>(sb + PA + p_off[i]) = m;
-                }
-        };
-        pload(0);
-        pstore(0);
-        __syncthreads();  // buffer 0 holds chunk 0
-        for (int cc = 0; cc < cpk; ++cc) {
-            if (cc + 1 < cpk) {
-                pload(cc + 1);
-                pstore((cc + 1) & 1);  // the buffer chunk cc - 1 used: every compute wave left it (last barrier)
-            }
-            __syncthreads();  // end of chunk cc
-        }
-    } else {
-        // ---- a compute wave: 128 px x 32 ch, weights one k-step ahead in registers
-        const int KS16 = a.K / 16, NB32 = (a.n_out + 31) / 32;
-        const uint32_t wplane_b = uint32_t(a.wplane) * 2u;
-        uint32_t w_base[TN];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int cb = (n0 >> 4) + wn * TN + j;
-            const int nb = cb >> 1;
-            w_base[j] = nb < NB32 ? uint32_t(nb * KS16 + (g >> 1)) * 1024u +
-                                        uint32_t(16 * (cb & 1) + l16 + 32 * (g & 1)) * 16u
-                                  : kOOB;
-        }
-        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(a.wsplit, 2u * wplane_b);
-        auto load_W = [&](int cc, int t, u32x4 (&wq)[2][TN]) {
-            const uint32_t ko = uint32_t(t * cpk + cc) * 2048u;
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    wq[p][j] = bload4u(rs_w, w_base[j] == kOOB ? kOOB : w_base[j] + ko + uint32_t(p) * wplane_b);
-        };
-        int a_hr[TM];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int p = i * 16 + l16;
-            a_hr[i] = (p / TW + 1) * HWD + (p % TW) + 1;
-        }
-        u32x4 wq[2][TN];
-        load_W(0, 0, wq);
-        __syncthreads();  // buffer 0 holds chunk 0
-        int cc = 0, t = 0;
-        for (int s = 0; s < nsteps; ++s) {
-            int t1 = t + 1, cc1 = cc;
-            if (t1 == a.ntaps) {
-                t1 = 0;
-                cc1 = cc + 1;
-            }
-            const unsigned char *const sbuf = smem + (cc & 1) * BUF;
-            const int toff = tap_at(a.tdy, t) * HWD + tap_at(a.tdx, t);
-            u32x4 wh[TN], wm_[TN], wl[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                wh[j] = wq[0][j];
-                wm_[j] = wq[1][j];
-                wl[j] = f16_down11(wh[j]);
-            }
-            if (s + 1 < nsteps) load_W(cc1, t1, wq);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int hr = a_hr[i] + toff;
-                const int ad = hr * 64 + (((g ^ (hr >> 1)) & 3) << 4);
-                const u32x4 xh = *reinterpret_cast<const u32x4 *>(sbuf + ad);
-                const u32x4 xm = *reinterpret_cast<const u32x4 *>(sbuf + PA + ad);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[j][i] = mfma16_f16(wl[j], xm, acc[j][i]);
-                    acc[j][i] = mfma16_f16(wm_[j], xh, acc[j][i]);
-                    acc[j][i] = mfma16_f16(wh[j], xh, acc[j][i]);
-                }
-            }
-            if (t1 == 0) __syncthreads();  // end of chunk cc: the producer has written chunk cc + 1
-            t = t1;
-            cc = cc1;
-        }
-        // undo the operand scales: per-channel weight inverse scales after the planes
-        const float *winv = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(a.wsplit) +
-                                                            2u * wplane_b);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + wn * WCH + j * 16 + 4 * g;
-            const f32x4 sc = (n < NB32 * 32 ? gload4(winv + n) : f32x4{0.f, 0.f, 0.f, 0.f}) * xs_inv;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) acc[j][i] *= sc;
-        }
-    }
-
-    // ---- epilogue (igemm_halo16_x3's, the producer joining its barriers only)
-    f32x4 bias4[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * WCH + j * 16 + 4 * g;
-        bias4[j] = (!producer && a.bias && n < a.n_out) ? *reinterpret_cast<const f32x4 *>(a.bias + n)
-                                                        : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    float omax = 0.f;
-    if (!producer) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int p = i * 16 + l16;
-            const size_t pix = size_t(img * a.ho + y0 + p / TW) * a.wo + x0 + (p % TW);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + wn * WCH + j * 16 + 4 * g;
-                if (n < a.n_out) {
-                    const f32x4 v = acc[j][i] + bias4[j];
-                    gstore4(a.dst + pix * a.ldc_d + n, v);
-                    omax = fmaxf(omax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-                }
-            }
-        }
-    }
-    if (a.dst_bound) wave_max_bound(a.dst_bound, fmaxf(omax, bound_seed(a)));  // uniform per wave; the producer adds 0
-
-    if (a.stat_rec) {
-        float *red1 = reinterpret_cast<float *>(smem);  // [WME][BN] sums
-        float *red2 = red1 + WME * BN;                  // [WME][BN] M2
-        if (!producer) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int q = 0; q < RG; ++q) {
-                        float sm = 0.f;
-#pragma unroll
-                        for (int i = q * TMG; i < (q + 1) * TMG; ++i) sm += acc[j][i][r] + bias4[j][r];
-                        sm = row16_sum(sm);
-                        if (l16 == 0) red1[q * BN + wn * WCH + j * 16 + 4 * g + r] = sm;
-                    }
-        }
-        __syncthreads();
-        if (!producer) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int nl = wn * WCH + j * 16 + 4 * g + r;
-                    float sm = 0.f;
-#pragma unroll
-                    for (int w = 0; w < WME; ++w) sm += red1[w * BN + nl];
-                    const float mean = sm * (1.f / float(BM));
-#pragma unroll
-                    for (int qg = 0; qg < RG; ++qg) {
-                        float q = 0.f;
-#pragma unroll
-                        for (int i = qg * TMG; i < (qg + 1) * TMG; ++i) {
-                            const float d = (acc[j][i][r] + bias4[j][r]) - mean;
-                            q = fmaf(d, d, q);
-                        }
-                        q = row16_sum(q);
-                        if (l16 == 0) red2[qg * BN + nl] = q;
-                    }
-                }
-        }
-        __syncthreads();
-        for (int nl = tid; nl < BN; nl += NT) {
-            if (n0 + nl >= a.n_out) continue;
-            float sm = 0.f, m2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < WME; ++w) {
-                sm += red1[w * BN + nl];
-                m2 += red2[w * BN + nl];
-            }
-            float *rec = a.stat_rec + (size_t(mt) * a.n_out + n0 + nl) * 2;
-            rec[0] = sm * (1.f / float(BM));
-            rec[1] = m2;
-        }
-    }
-
-    if (a.bb_rec) {
-        float *red1 = reinterpret_cast<float *>(smem);
-        float *red2 = red1 + WME * BN;
-        if (!producer) {
-            const int co = (img / a.bb_seg_imgs) * a.n_out;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + wn * WCH + j * 16 + 4 * g;
-                const bool nok = n < a.n_out;
-                const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-                const f32x4 mu = nok ? gload4(a.bb_mean + co + n) : z4, iv = nok ? gload4(a.bb_inv + co + n) : z4;
-                const f32x4 sc = nok ? gload4(a.bb_scale + co + n) : z4, sf = nok ? gload4(a.bb_shift + co + n) : z4;
-#pragma unroll
-                for (int qg = 0; qg < RG; ++qg) {
-                    f32x4 s1 = z4, s2 = z4;
-#pragma unroll
-                    for (int i = qg * TMG; i < (qg + 1) * TMG; ++i) {
-                        const int p = i * 16 + l16;
-                        const size_t pix = size_t(img * a.ho + y0 + p / TW) * a.wo + x0 + (p % TW);
-                        const f32x4 y4 = nok ? gload4(a.bb_y + pix * a.bb_ldy + n) : z4;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float dz = fmaf(y4[r], sc[r], sf[r]) > 0.f ? acc[j][i][r] : 0.f;
-                            s1[r] += dz;
-                            s2[r] += dz * ((y4[r] - mu[r]) * iv[r]);
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float t1 = row16_sum(s1[r]), t2 = row16_sum(s2[r]);
-                        if (l16 == 0) {
-                            red1[qg * BN + wn * WCH + j * 16 + 4 * g + r] = t1;
-                            red2[qg * BN + wn * WCH + j * 16 + 4 * g + r] = t2;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        for (int nl = tid; nl < BN; nl += NT) {
-            if (n0 + nl >= a.n_out) continue;
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < WME; ++w) {
-                t1 += red1[w * BN + nl];
-                t2 += red2[w * BN + nl];
-            }
-            float *rec = a.bb_rec + (size_t(n0 + nl) * a.bb_ntiles + mt) * 2;
-            rec[0] = t1;
-            rec[1] = t2;
-        }
-    }
-}
-
 namespace {
 
 struct H16Cfg {
@@ -1191,29 +855,6 @@ void launch16_1xn_bf16(const IgemmArgs &a, int tw, hipStream_t s) {
         launch16c<WM, WN, TM, TN, OCC, false, 1>(a, tw, s);
 }
 
-// The warp-specialized form of the 1 x N tiles (igemm_halo16_ws): WN compute waves + one producer wave per block.
-template <int WN, int TM, int TN, int OCC, bool IN_BN>
-void launch_ws_b(const IgemmArgs &a, int tw, hipStream_t s) {
-    constexpr int BM = TM * 16, BN = WN * TN * 16;
-    IgemmArgs b = a;
-    b.grid_m = a.n_img * (a.ho / (BM / tw)) * (a.wo / tw);
-    b.grid_n = (a.n_out + BN - 1) / BN;
-    b.remap = halo_remap(a.tune);
-    const dim3 grid(b.grid_m * b.grid_n), block(64 * (WN + 1));
-    (void)tw;  // 16: halo16_ws only takes maps tiled by 16-wide tiles (halo16_pick's first choice)
-    hipLaunchKernelGGL((igemm_halo16_ws<WN, TM, TN, 16, OCC, IN_BN>), grid, block, 0, s, b);
-}
-template <int WN, int TM, int TN, int OCC>
-void launch_ws(const IgemmArgs &a, int tw, hipStream_t s) {
-    if (a.in_scale)
-        launch_ws_b<WN, TM, TN, OCC, true>(a, tw, s);
-    else
-        launch_ws_b<WN, TM, TN, OCC, false>(a, tw, s);
-}
-bool halo16_ws(const IgemmArgs &a) {
-    return (a.tune & SCD_TUNE_HALO16_WS) && wide_1xn_ok(a) && !a.sb && a.wo % 16 == 0 && a.ho % 8 == 0;
-}
-
 }  // namespace
 
 // 0 when `a` does not take this kernel, else 1 + config id; *bm = pixels per tile, *tw = tile width.
@@ -1242,7 +883,6 @@ int halo16_pick(const IgemmArgs &a, bool eligible, int *bm, int *tw) {
     else
         return 0;
     if (id < 0 || id > 5 || (id > 2 && !wide_1xn_ok(a) && !bf16_1xn(a))) return 0;
-    if (id == 5 && halo16_ws(a)) id = 4;  // the warp-specialized blocks tile 128 pixels
     for (;;) {
         *bm = kCfg[id].bm;
         const int pref = 16;  // preferred tile width, the smallest halo per pixel (180 rows for 128 px)
@@ -1284,18 +924,8 @@ void launch_halo16(const IgemmArgs &a, int cfg, int tw, hipStream_t s) {
     switch (cfg - 1) {
         case 0: launch16<2, 2, 4, 4, 2>(a, tw, s); break;
         case 1: launch16<2, 2, 4, 2, 3>(a, tw, s); break;
-        case 3:
-            if (halo16_ws(a))
-                launch_ws<4, 8, 2, 2>(a, tw, s);
-            else
-                launch16_1xn<1, 4, 8, 2, 2>(a, tw, s);
-            break;
-        case 4:
-            if (halo16_ws(a))
-                launch_ws<2, 8, 2, 3>(a, tw, s);
-            else
-                launch16_1xn<1, 2, 8, 2, 2>(a, tw, s);
-            break;
+        case 3: launch16_1xn<1, 4, 8, 2, 2>(a, tw, s); break;
+        case 4: launch16_1xn<1, 2, 8, 2, 2>(a, tw, s); break;
         case 5: launch16_1xn<2, 2, 8, 2, 2>(a, tw, s); break;
         default: launch16<2, 2, 2, 4, 3>(a, tw, s); break;
     }
@@ -1818,19 +1448,15 @@ __device__ __forceinline__ void w16_chain(f32x4 (&acc)[9][W16L<LC>::CB][W16L<LC>
 // RG = 2 (LC 1 only): a block of 8 waves owns 128 rows r x 64 channels c; the two 4-wave groups share the
 // staged X halo, which is then split and stored once per 128 rows instead of per 64 (the staging per MFMA,
 // a third of the kernel's time at RG 1, drops by ~35%).
-// DB (SCD_TUNE_WGRAD16_DB): two patch buffers, one barrier per patch; with RG 2 the second 4-wave group (waves 4-7,
-// the partners of waves 0-3 on their SIMDs) stores the next patch BEFORE its MFMAs while the first group stores it
-// after them, so one wave of each SIMD pair stages while the other computes (a stagger: without it both reach
-// their split + LDS writes, and the matrix cores idle, together).
 // RBN: the rows are dL/da of a = relu(BN(y)) and every dY element is formed while staging (bn_bwd_dy4, the expression
 // of bn_bwd_apply: bit-identical values), with the BatchNorm coefficients of the block's rows held in LDS for both
 // segments; the blocks of channel tile 0 also store the formed dY (a.rows_out) for the data grad, which then reads
 // it as before: the separate BatchNorm-backward apply pass (read y and da, write dy) and this kernel's read of dy
 // become this kernel's read of y and da.
-template <int NP, int LC, int RG, bool SB = false, bool DB = false, bool RBN = false>
+template <int NP, int LC, int RG, bool SB = false, bool RBN = false>
 __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a) {
     static_assert(!SB || NP == 1, "bf16 storage runs the bf16 arithmetic");
-    static_assert(!RBN || (LC == 1 && !DB && (NP == 1 || NP == 4)), "rows transform: h2 / bf16, along-c layout");
+    static_assert(!RBN || (LC == 1 && (NP == 1 || NP == 4)), "rows transform: h2 / bf16, along-c layout");
     constexpr uint32_t EB = SB ? 2u : 4u;
     constexpr int NT = 256 * RG;
     constexpr int PH = 2, PW = 16, P = PH * PW;
@@ -1853,7 +1479,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
     // kernels sit at 256 VGPRs; eight more for y spilled the 64-row block)
     constexpr bool YDMA = RBN && H2;
     constexpr int YST = YDMA ? A_PER * NT * 16 : 0;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[(DB ? 2 : 1) * STAGE + COEF + YST];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGE + COEF + YST];
     float ds = 1.f, ds_inv = 1.f, xs = 1.f, xs_inv = 1.f;  // h2: power-of-two operand scales
     if constexpr (H2) {
         h2_scale(*a.rows_bound, ds, ds_inv);
@@ -1881,7 +1507,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
     float omax = 0.f;                                  // RBN writer: max |dY| stored by this lane
 
     StageT<SB> ra[A_PER], rb[B_PER], ya[RBN && !YDMA ? A_PER : 1];
-    unsigned char *const ystage = smem + (DB ? 2 : 1) * STAGE + COEF;  // YDMA: piece e of the patch at e * 16
+    unsigned char *const ystage = smem + STAGE + COEF;  // YDMA: piece e of the patch at e * 16
     const int wave_u = __builtin_amdgcn_readfirstlane(wid);
     f32x4 x_sc, x_sh;      // src transform coefficients of this thread's 4 channels (cq = tid & 15)
     uint32_t x_valid = 0;  // bit i: halo piece i is inside the image (the padding stays zero)
@@ -1920,8 +1546,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
             rb[i] = bload_q<SB>(rs_src, v ? uint32_t(((img * a.hs + sy) * a.ws + sx) * a.ldc_s + c0 + cq * 4) * EB : kOOB);
         }
     };
-    auto store_patch = [&](int buf) {
-        unsigned char *const smem_b = smem + buf * STAGE;
+    auto store_patch = [&]() {
         // h2: the scale folds into the transform exactly; applied here, not behind the coefficient loads, where the
         // compiler waited for them (vmcnt in order: the wave stalled at issue)
         const f32x4 sc = H2 ? x_sc * xs : x_sc, sh = H2 ? x_sh * xs : x_sh;
@@ -1935,8 +1560,8 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
                 // dY of this piece from y and dL/da: bn_bwd_apply's expression (stored4: one rounding to the storage
                 // type), the writer blocks store it, then it is staged as a plain dY piece
                 const int cq = e % CQ, q = e / CQ;
-                const float *cf = reinterpret_cast<const float *>(smem + (DB ? 2 : 1) * STAGE) +
-                                  (st_img / a.rows_seg_imgs) * 7 * RBLK + cq * 4;
+                const float *cf =
+                    reinterpret_cast<const float *>(smem + STAGE) + (st_img / a.rows_seg_imgs) * 7 * RBLK + cq * 4;
                 const f32x4 mu = *reinterpret_cast<const f32x4 *>(cf), iv = *reinterpret_cast<const f32x4 *>(cf + RBLK);
                 const f32x4 sc = *reinterpret_cast<const f32x4 *>(cf + 2 * RBLK);
                 const f32x4 sf = *reinterpret_cast<const f32x4 *>(cf + 3 * RBLK);
@@ -1971,15 +1596,15 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
                     split2h_pre(ra[i] * ds, h, m);
                 else
                     split2h(ra[i] * ds, h, m);
-                *reinterpret_cast<u32x2 *>(smem_b + PA + o) = m;
+                *reinterpret_cast<u32x2 *>(smem + PA + o) = m;
             } else if constexpr (DP == 3) {
                 split3(ra[i], h, m, l);
-                *reinterpret_cast<u32x2 *>(smem_b + PA + o) = m;
-                *reinterpret_cast<u32x2 *>(smem_b + 2 * PA + o) = l;
+                *reinterpret_cast<u32x2 *>(smem + PA + o) = m;
+                *reinterpret_cast<u32x2 *>(smem + 2 * PA + o) = l;
             } else {
                 h = stage_bits<SB>(ra[i]);
             }
-            *reinterpret_cast<u32x2 *>(smem_b + o) = h;
+            *reinterpret_cast<u32x2 *>(smem + o) = h;
         }
 #pragma unroll
         for (int i = 0; i < B_PER; ++i)
@@ -1994,7 +1619,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
                         h = pk_bf16x4(x);
                     }
                     const int e = tid + i * NT;
-                    *reinterpret_cast<u32x2 *>(smem_b + DP * PA + (e >> 4) * RS + (e & 15) * 8) = h;
+                    *reinterpret_cast<u32x2 *>(smem + DP * PA + (e >> 4) * RS + (e & 15) * 8) = h;
                 }
             } else if (tid + i * NT < B_CH) {
                 u32x2 h, m, l;
@@ -2009,16 +1634,16 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
                 const int o = DP * PA + (e >> 4) * RS + (e & 15) * 8;
                 if constexpr (H2) {
                     split2h(rb[i], h, m);
-                    *reinterpret_cast<u32x2 *>(smem_b + PB + o) = m;
+                    *reinterpret_cast<u32x2 *>(smem + PB + o) = m;
                 } else if constexpr (XP >= 2) {
                     split3(rb[i], h, m, l);  // x5: the l term is not needed (dead code)
-                    *reinterpret_cast<u32x2 *>(smem_b + PB + o) = m;
-                    if constexpr (XP == 3) *reinterpret_cast<u32x2 *>(smem_b + 2 * PB + o) = l;
+                    *reinterpret_cast<u32x2 *>(smem + PB + o) = m;
+                    if constexpr (XP == 3) *reinterpret_cast<u32x2 *>(smem + 2 * PB + o) = l;
                 } else {
                     h[0] = cvt_pk_bf16(rb[i][0], rb[i][1]);
                     h[1] = cvt_pk_bf16(rb[i][2], rb[i][3]);
                 }
-                *reinterpret_cast<u32x2 *>(smem_b + o) = h;
+                *reinterpret_cast<u32x2 *>(smem + o) = h;
             }
     };
 
@@ -2038,7 +1663,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
     const uint32_t xbase = lds_addr(smem) + DP * PA + (py * HW_ + pxq) * RS + (16 * NCB * wj + 4 * (w16 & 3)) * 2;
 
     if constexpr (RBN) {  // the block's rows' BatchNorm coefficients, both segments (launcher: at most 2 per launch)
-        float *cf = reinterpret_cast<float *>(smem + (DB ? 2 : 1) * STAGE);
+        float *cf = reinterpret_cast<float *>(smem + STAGE);
         const int nsl = a.n_img_w / a.rows_seg_imgs;
         for (int e = tid; e < nsl * RBLK; e += NT) {
             const int sg = e / RBLK, r = e - sg * RBLK, o = sg * a.R + r0 + r;
@@ -2055,36 +1680,21 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
         __syncthreads();
     }
     if (pbeg < pend) {
-        // DB, RG 2: waves 4-7 stage the next patch before their MFMAs (loads two patches ahead), waves 0-3 after
-        const bool early = DB && RG == 2 && __builtin_amdgcn_readfirstlane(wid) >= 4;
         load_patch(pbeg);
-        store_patch(0);
-        if (early && pbeg + 1 < pend) load_patch(pbeg + 1);
+        store_patch();
         __syncthreads();
-        int buf = 0;
         for (int pi = pbeg; pi < pend; ++pi) {
             const bool more = pi + 1 < pend;
-            if (early) {
-                // the buffer of patch pi + 1 was last read in the previous patch, which the barrier closed
-                if (more) store_patch(buf ^ 1);
-                if (pi + 2 < pend) load_patch(pi + 2);
-            } else if (more) {
-                load_patch(pi + 1);
-            }
-            const uint32_t bo = uint32_t(buf * STAGE);
+            if (more) load_patch(pi + 1);
             bf16x8 dv[3][NRB];
-            w16_read_dy<0, PA, NRB, DP, RSD>(dv, dbase + bo);
+            w16_read_dy<0, PA, NRB, DP, RSD>(dv, dbase);
             s16x4 f0[6], f1[6];
-            w16_read_x<0 / NCB, 0 % NCB, PB, HW_, NP>(f0, xbase + bo);
-            w16_read_x<1 / NCB, 1 % NCB, PB, HW_, NP>(f1, xbase + bo);
-            w16_chain<0, PB, HW_, NP, LC>(acc, dv, f0, f1, xbase + bo);
-            if constexpr (DB) {
-                if (!early && more) store_patch(buf ^ 1);
-                __syncthreads();  // patch pi + 1 is staged; every wave is done with patch pi
-                buf ^= 1;
-            } else if (more) {
+            w16_read_x<0 / NCB, 0 % NCB, PB, HW_, NP>(f0, xbase);
+            w16_read_x<1 / NCB, 1 % NCB, PB, HW_, NP>(f1, xbase);
+            w16_chain<0, PB, HW_, NP, LC>(acc, dv, f0, f1, xbase);
+            if (more) {
                 __syncthreads();  // every wave is done with this patch
-                store_patch(0);
+                store_patch();
                 __syncthreads();
             }
         }
@@ -2168,6 +1778,8 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_dma(WgradArgs a
     constexpr int RCH = RBN ? P * DCH / NT : 0;       // RBN: dY chunks each thread forms (and the writer stores) per patch
     constexpr int CFX = XT ? 2 * 2 * 64 * 4 : 0;      // XT: [segment 2][sc, sh][64 channels] floats
     constexpr int CFR = RBN ? 2 * 7 * RBLK * 4 : 0;   // RBN: [segment 2][7 coefficients][RBLK] (wgrad_halo16_x3's)
+    static_assert(NB * STAGE + kDmaSink + CFX + CFR <= 160 * 1024,
+                  "ring depth NB: NB patch buffers and the coefficient tables exceed the CU's 160 KB of LDS");
     __shared__ __attribute__((aligned(16))) unsigned char smem[NB * STAGE + kDmaSink + CFX + CFR];
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -2813,15 +2425,6 @@ static const void *w16_kernel(int lc, int rb) {
 }
 template <int NP, bool SB = false>
 static void w16_launch(int lc, int rb, const WgradArgs &a, dim3 grid, hipStream_t s) {
-    if constexpr (NP == 4 && !SB) {
-        if ((a.tune & SCD_TUNE_WGRAD16_DB) && lc) {
-            if (rb == 128)
-                hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 2, false, true>), grid, dim3(512), 0, s, a);
-            else
-                hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 1, false, true>), grid, dim3(256), 0, s, a);
-            return;
-        }
-    }
     if (rb == 128)
         hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 2, SB>), grid, dim3(512), 0, s, a);
     else if (lc)
@@ -2843,13 +2446,13 @@ const void *wgrad_halo16_fn(int math, uint32_t tune, bool bounded, int rblock) {
 template <int NP, bool SB>
 static void w16_launch_rbn(int rb, const WgradArgs &a, dim3 grid, hipStream_t s) {
     if (rb == 128)
-        hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 2, SB, false, true>), grid, dim3(512), 0, s, a);
+        hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 2, SB, true>), grid, dim3(512), 0, s, a);
     else
-        hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 1, SB, false, true>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 1, SB, true>), grid, dim3(256), 0, s, a);
 }
 bool wgrad16_rows_bn_ok(int math, uint32_t tune, bool bounded) {
     const int np = wgrad16_planes(math, tune, bounded);
-    return (np == 1 || np == 4) && w16_layout(tune) && !(tune & SCD_TUNE_WGRAD16_DB);
+    return (np == 1 || np == 4) && w16_layout(tune);
 }
 // a.grid_r = R / wgrad16_rblock(...) (the caller plans with the same choice).
 void launch_wgrad_halo16_x3(const WgradArgs &a, dim3 grid, hipStream_t s) {
