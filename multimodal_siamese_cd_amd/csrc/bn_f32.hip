@@ -10,6 +10,8 @@
 //              Chan-merged in LDS, so there is no E[x^2]-E[x]^2 cancellation.  Records are written
 //              channel-major, rec[c][chunk][field].
 //   finalize : one workgroup per channel merges its chunk records in double with a fixed-shape tree.
+#include <type_traits>
+
 #include "common.h"
 
 namespace scd {
@@ -331,10 +333,12 @@ struct DaPlain {  // a materialised tensor
 // MaxPool2d backward of the next level's input gradient gy through the argmax bytes, plus -/+ the gradient of
 // the Siamese feature difference (skip_mode 1: t1 images subtract) or a plain skip gradient (skip_mode 0).
 // skip_mode 2 (the dual-task encoder): also the semantic decoder's skip gradient gs2, a [t2; t1] batch of 2 gsn images
-// (image img of the [t1; t2] level reads gs2 image img + gsn for t1, img - gsn for t2), added to the difference term
-// first: (sg * gs + gs2) is the one rounding autograd's sum of the two skip gradients makes.
+// (image img of the [t1; t2] level reads gs2 image img + gsn for t1, img - gsn for t2).
+// It is walked over 2x2 cells: cell (img, cy, cx) covers the full-resolution pixels (2cy + i, 2cx + j) that exist
+// (ceil(h/2) x ceil(w/2) cells per image), so the pooled gradient and its argmax bytes are read and decoded once per
+// cell instead of once per pixel, with the cell's four pixels' loads in flight together.
 template <class T>
-struct DaPooled {
+struct PooledCells {
     const T *gy;  // (n, h/2, w/2, C) or null
     const uint8_t *idx;
     int hy, wy, ldgy;
@@ -343,46 +347,9 @@ struct DaPooled {
     const T *gs2;  // skip_mode 2: (2 gsn, h, w, C), else null
     int ldgs2;
     int hx, wx, C;
-    FastDiv div_hw, div_w, div_gsn;
-    __device__ __forceinline__ void bind(int) {}
-    __device__ __forceinline__ f4 operator()(int64_t p, int c) const {
-        const uint32_t img = fdiv(uint32_t(p), div_hw);
-        const uint32_t rr = uint32_t(p) - img * uint32_t(hx * wx);
-        const int yy = int(fdiv(rr, div_w)), x = int(rr) - yy * wx;
-        f4 r = {0.f, 0.f, 0.f, 0.f};
-        if (gy) {
-            const int oy = yy >> 1, ox = x >> 1;
-            if (oy < hy && ox < wy) {
-                const int64_t q = (int64_t(img) * hy + oy) * wy + ox;
-                const uint32_t pk = *reinterpret_cast<const uint32_t *>(idx + q * C + c);
-                const f4 g = ld4(gy + q * ldgy + c);
-                const uint32_t want = uint32_t((yy & 1) * 2 + (x & 1));
-                r.x = ((pk >> 0) & 0xff) == want ? g.x : 0.f;
-                r.y = ((pk >> 8) & 0xff) == want ? g.y : 0.f;
-                r.z = ((pk >> 16) & 0xff) == want ? g.z : 0.f;
-                r.w = ((pk >> 24) & 0xff) == want ? g.w : 0.f;
-            }
-        }
-        if (gs) {
-            const int simg = int(img - fdiv(img, div_gsn) * uint32_t(gsn));
-            const float sg = (skip_mode != 0 && int(img) < gsn) ? -1.f : 1.f;
-            const f4 sv = ld4(gs + ((int64_t(simg) * hx + yy) * wx + x) * ldgs + c);
-            if (gs2) {
-                const int img2 = int(img) < gsn ? int(img) + gsn : int(img) - gsn;
-                const f4 s2 = ld4(gs2 + ((int64_t(img2) * hx + yy) * wx + x) * ldgs2 + c);
-                r.x += sg * sv.x + s2.x;
-                r.y += sg * sv.y + s2.y;
-                r.z += sg * sv.z + s2.z;
-                r.w += sg * sv.w + s2.w;
-            } else {
-                r.x += sg * sv.x;
-                r.y += sg * sv.y;
-                r.z += sg * sv.z;
-                r.w += sg * sv.w;
-            }
-        }
-        return r;
-    }
+    FastDiv div_gsn;
+    int ch, cw;                // cells per image column / row
+    FastDiv div_cimg, div_cw;  // ch * cw, cw
 };
 
 // The decoder's last gradient when the 1x1 head reads its output: dL/da = sum_o gout[img][o][pix] * w[o][c], formed on
@@ -393,21 +360,6 @@ struct DaHead {
     const float *w;  // [n_out][C]
     int n_out, C, hw;
     FastDiv div_hw;
-    __device__ __forceinline__ void bind(int) {}
-    __device__ __forceinline__ f4 operator()(int64_t p, int c) const {
-        const uint32_t img = fdiv(uint32_t(p), div_hw);
-        const int pix = int(uint32_t(p) - img * uint32_t(hw));
-        f4 r = {0.f, 0.f, 0.f, 0.f};
-        for (int o = 0; o < n_out; ++o) {
-            const float gv = g[(int64_t(img) * n_out + o) * hw + pix];
-            const float *wr = w + int64_t(o) * C + c;
-            r.x = fmaf(gv, wr[0], r.x);
-            r.y = fmaf(gv, wr[1], r.y);
-            r.z = fmaf(gv, wr[2], r.z);
-            r.w = fmaf(gv, wr[3], r.w);
-        }
-        return r;
-    }
 };
 
 // DaHead with the head count a compile-time constant and the thread's weight quads held in registers (bind, once per
@@ -441,25 +393,14 @@ struct DaHeadN {
     }
 };
 
-// The DaPooled gradient over 2x2 cells: cell (img, cy, cx) covers the full-resolution pixels (2cy + i, 2cx + j) that
-// exist (ceil(h/2) x ceil(w/2) cells per image), so the pooled gradient and its argmax bytes are read and decoded once
-// per cell instead of once per pixel, with the cell's four pixels' loads in flight together.
-template <class T>
-struct PooledCells {
-    DaPooled<T> da;
-    int ch, cw;                 // cells per image column / row
-    FastDiv div_cimg, div_cw;   // ch * cw, cw
-};
-
 // dL/da of the four pixels of `cell` (flat cell index over images) at channel quad c; ok[k]: pixel k exists.
-// S2: the dual-task second skip gradient (DaPooled.gs2, with gs present).
+// S2: the dual-task second skip gradient (gs2, with gs present).
 template <class T, bool S2>
-__device__ __forceinline__ void cell_grads(const PooledCells<T> &P, uint32_t cell, int c, f4 (&g)[4], int64_t (&pix)[4],
+__device__ __forceinline__ void cell_grads(const PooledCells<T> &d, uint32_t cell, int c, f4 (&g)[4], int64_t (&pix)[4],
                                            bool (&ok)[4], const T *fallback) {
-    const DaPooled<T> &d = P.da;
-    const uint32_t img = fdiv(cell, P.div_cimg);
-    const uint32_t r = cell - img * uint32_t(P.ch * P.cw);
-    const int cy = int(fdiv(r, P.div_cw)), cx = int(r) - cy * P.cw;
+    const uint32_t img = fdiv(cell, d.div_cimg);
+    const uint32_t r = cell - img * uint32_t(d.ch * d.cw);
+    const int cy = int(fdiv(r, d.div_cw)), cx = int(r) - cy * d.cw;
     // Every load is unconditional (addresses clamped into the maps, the values selected afterwards), so a cell's
     // loads issue together: guarded loads had each waited for the previous one (one memory latency per pixel).
     // No branches around the loads either: a missing operand (no pooled gradient, no skip) reads `fallback` (valid
@@ -497,6 +438,8 @@ __device__ __forceinline__ void cell_grads(const PooledCells<T> &P, uint32_t cel
         // the skip term of a missing pixel (ok[k] false) reads a clamped neighbour: its g is never used; a select,
         // not a branch, so the caller's loads can be scheduled above
         if constexpr (S2) {
+            // the second skip gradient is added to the difference term first: (sg * gs + gs2) is the one rounding
+            // autograd's sum of the two skip gradients makes
             const f4 u = {sg * sv[k].x + s2v[k].x, sg * sv[k].y + s2v[k].y, sg * sv[k].z + s2v[k].z,
                           sg * sv[k].w + s2v[k].w};
             g[k] = v + u;
@@ -517,12 +460,11 @@ __device__ __forceinline__ int64_t cell_load_pix(const int64_t (&pix)[4], const 
 // cell (same place) in image img + gsn.  The difference gradient is read once for both (t1 subtracts it, t2 adds
 // it, with cell_grads' expressions: bit-identical).  pix[k] is the t1 pixel; its t2 partner is pix[k] + gsn*hx*wx.
 template <class T, bool S2>
-__device__ __forceinline__ void cell_grads_pair(const PooledCells<T> &P, uint32_t cell, int c, f4 (&g0)[4], f4 (&g1)[4],
+__device__ __forceinline__ void cell_grads_pair(const PooledCells<T> &d, uint32_t cell, int c, f4 (&g0)[4], f4 (&g1)[4],
                                                 int64_t (&pix)[4], bool (&ok)[4]) {
-    const DaPooled<T> &d = P.da;
-    const uint32_t img = fdiv(cell, P.div_cimg);
-    const uint32_t r = cell - img * uint32_t(P.ch * P.cw);
-    const int cy = int(fdiv(r, P.div_cw)), cx = int(r) - cy * P.cw;
+    const uint32_t img = fdiv(cell, d.div_cimg);
+    const uint32_t r = cell - img * uint32_t(d.ch * d.cw);
+    const int cy = int(fdiv(r, d.div_cw)), cx = int(r) - cy * d.cw;
     // unconditional loads (clamped addresses, values selected afterwards): see cell_grads
     // a missing pooled gradient reads the skip gradient's memory (valid; discarded): no branch around the loads
     const bool has_gy = d.gy && d.hy > 0 && d.wy > 0;  // uniform
@@ -558,7 +500,7 @@ __device__ __forceinline__ void cell_grads_pair(const PooledCells<T> &P, uint32_
                  ((pk0 >> 16) & 0xff) == want ? gp0.z : 0.f, ((pk0 >> 24) & 0xff) == want ? gp0.w : 0.f};
         f4 v1 = {((pk1 >> 0) & 0xff) == want ? gp1.x : 0.f, ((pk1 >> 8) & 0xff) == want ? gp1.y : 0.f,
                  ((pk1 >> 16) & 0xff) == want ? gp1.z : 0.f, ((pk1 >> 24) & 0xff) == want ? gp1.w : 0.f};
-        if constexpr (S2) {  // (sg * gs + gs2) first: see DaPooled
+        if constexpr (S2) {  // (sg * gs + gs2) first: see cell_grads
             const f4 sv = svs[k];
             const float m = -1.f, p1 = 1.f;
             v0 += f4{m * sv.x + s2a[k].x, m * sv.y + s2a[k].y, m * sv.z + s2a[k].z, m * sv.w + s2a[k].w};
@@ -580,52 +522,120 @@ __device__ __forceinline__ void cell_grads_pair(const PooledCells<T> &P, uint32_
     }
 }
 
-// Block-wide tree sum of (a, b) per channel quad into rec[c][rec_idx][2] (bn_bwd_pooled_partial's tree and layout).
-__device__ __forceinline__ void pooled_rec2(f4 (&sh1)[BN_THREADS], f4 (&sh2)[BN_THREADS], f4 a, f4 b, int tid, int pl,
-                                            int npl, int qpb, int c, int C, int nrec, int rec_idx,
-                                            float *__restrict__ rec) {
-    sh1[tid] = a;
-    sh2[tid] = b;
+// What the backward kernels take besides their tensors: the walk's geometry and the coefficient arrays.
+struct BnWalk {
+    int C;
+    int64_t lseg;  // pixels (the cell kernels: cells) per segment
+    int ncps, chunk, nrec, qpb;
+    const float *smean, *sinv, *gamma, *scale, *shift;  // [seg][C]; gamma [C] or null (apply kernels)
+    const float *coef;                                  // [seg][C][2] = {k1, k2} of bn_bwd_finalize (apply kernels)
+};
+__device__ __forceinline__ Chunk chunk_of(const BnWalk &w) { return chunk_of(w.lseg, w.ncps, w.chunk); }
+
+// A thread's place in its block: pixel lane pl of npl, channel quad tid % qpb of the block's qpb (channels c .. c + 3).
+struct Lane {
+    int tid, pl, npl, qpb, c;
+};
+__device__ __forceinline__ Lane lane_of(int qpb) {
+    const int tid = threadIdx.x;
+    return Lane{tid, tid / qpb, BN_THREADS / qpb, qpb, int(blockIdx.y * qpb + tid % qpb) * 4};
+}
+
+// One segment's constants of channel quad c: the partial kernels' ...
+struct SegStat {
+    f4 mu, iv, sc, sf;
+    // o = seg * C + c
+    __device__ __forceinline__ void load(int o, const float *smean, const float *sinv, const float *scale,
+                                         const float *shift) {
+        mu = ld4(smean + o), iv = ld4(sinv + o), sc = ld4(scale + o), sf = ld4(shift + o);
+    }
+    __device__ __forceinline__ void load(int seg, int c, const BnWalk &w) {
+        load(seg * w.C + c, w.smean, w.sinv, w.scale, w.shift);
+    }
+    __device__ __forceinline__ f4 dz(f4 y, f4 g) const { return relu_mask(y, sc, sf, g); }
+    __device__ __forceinline__ f4 xhat(f4 y) const { return (y - mu) * iv; }
+};
+// ... and with the apply kernels' k1, k2 (de-interleaved from coef) and mul = gamma * invstd.
+struct SegCoef : SegStat {
+    f4 k1, k2, mul;
+    __device__ __forceinline__ void load(int seg, int c, const BnWalk &w) {
+        SegStat::load(seg, c, w);
+        const float *cf = w.coef + size_t(seg * w.C + c) * 2;
+        k1 = f4{cf[0], cf[2], cf[4], cf[6]};
+        k2 = f4{cf[1], cf[3], cf[5], cf[7]};
+        const f4 gm = w.gamma ? ld4(w.gamma + c) : f4{1.f, 1.f, 1.f, 1.f};
+        mul = gm * iv;
+    }
+    // the value stored to dy (rounded to T's storage)
+    template <class T>
+    __device__ __forceinline__ f4 dy(const T *dst, f4 y, f4 g) const {
+        return stored4(dst, bn_bwd_dy4(y, g, mu, iv, sc, sf, k1, k2, mul));
+    }
+};
+
+// The block epilogue of the backward and channel-sum kernels.  Every thread holds N sums of its channel quad over its
+// lane's pixels; block_tree_sum adds the lanes in a fixed tree (off = npl/2 .. 1, partner tid + off*qpb) and leaves
+// the totals in sh[.][tid] of lane 0's threads.
+template <int N>
+__device__ __forceinline__ void block_tree_sum(f4 (&sh)[N][BN_THREADS], const f4 (&v)[N], const Lane &L) {
+    const int tid = L.tid, pl = L.pl, npl = L.npl, qpb = L.qpb;
+#pragma unroll
+    for (int i = 0; i < N; ++i) sh[i][tid] = v[i];
     __syncthreads();
     for (int off = npl / 2; off > 0; off >>= 1) {
         if (pl < off) {
-            sh1[tid] += sh1[tid + off * qpb];
-            sh2[tid] += sh2[tid + off * qpb];
+#pragma unroll
+            for (int i = 0; i < N; ++i) sh[i][tid] += sh[i][tid + off * qpb];
         }
         __syncthreads();
     }
-    if (pl == 0 && c < C) {
-        const f4 x = sh1[tid], y = sh2[tid];
-        const float xv[4] = {x.x, x.y, x.z, x.w}, yv[4] = {y.x, y.y, y.z, y.w};
+}
+// A lane-0 thread stores its totals sum[0..NF) as the NF-field record rec[c + k][rec_idx] of its four channels
+// (channel-major records, nrec per channel).
+template <int NF>
+__device__ __forceinline__ void store_rec(const f4 (*sum)[BN_THREADS], int c, int nrec, int64_t rec_idx,
+                                          float *__restrict__ rec) {
+    float av[NF][4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float *r = rec + (size_t(c + k) * nrec + rec_idx) * 2;
-            r[0] = xv[k];
-            r[1] = yv[k];
-        }
+    for (int f = 0; f < NF; ++f) {
+        const f4 a = sum[f][threadIdx.x];
+        av[f][0] = a.x, av[f][1] = a.y, av[f][2] = a.z, av[f][3] = a.w;
     }
-    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float *r = rec + (size_t(c + k) * nrec + rec_idx) * NF;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) r[f] = av[f][k];
+    }
+}
+// Both: rec[c][rec_idx][N] = the block's sums of v.  REUSE: a trailing barrier, so that sh can take the next call.
+// The kernels accumulate in named registers and form v at the call (summing into an array cost
+// bn_bwd_pooled_partial<float, true> two VGPRs and bn_bwd_partial_head<float, 2> its load grouping); rec_idx is 64 bits wide so that each caller's 32-bit index, signed or
+// not, extends as it did when the epilogue was written out in the kernel.
+template <int N, bool REUSE = false>
+__device__ __forceinline__ void block_rec(f4 (&sh)[N][BN_THREADS], const f4 (&v)[N], const Lane &L, int C, int nrec,
+                                          int64_t rec_idx, float *__restrict__ rec) {
+    block_tree_sum(sh, v, L);
+    if (L.pl == 0 && L.c < C) store_rec<N>(sh, L.c, nrec, rec_idx, rec);
+    if constexpr (REUSE) __syncthreads();
 }
 
 // bn_bwd_pooled_partial for a Siamese pair: block k covers chunk k of the t1 segment and chunk k of the t2 segment
 // (same cells), reading the shared difference gradient once; same per-chunk records, bit-identical.
 template <class T, bool S2>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_partial_pair(const T *__restrict__ y, int ldy,
-                                                                         PooledCells<T> P, int C, int64_t cseg, int ncps,
-                                                                         int chunk, int nrec, int qpb,
-                                                                         const float *smean, const float *sinv,
-                                                                         const float *scale, const float *shift,
+                                                                         PooledCells<T> P, BnWalk w,
                                                                          float *__restrict__ rec) {
-    __shared__ f4 sh1[BN_THREADS], sh2[BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
-    const Chunk ch = chunk_of(cseg, ncps, chunk);  // blockIdx.x < ncps: the t1 segment's chunk
-    const int64_t poff = int64_t(P.da.gsn) * P.da.hx * P.da.wx;
+    __shared__ f4 sh[2][BN_THREADS];
+    const Lane L = lane_of(w.qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
+    const Chunk ch = chunk_of(w);  // blockIdx.x < ncps: the t1 segment's chunk
+    const int64_t poff = int64_t(P.gsn) * P.hx * P.wx;
     f4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = a1, b1 = a1, b2 = a1;
-    if (c < C) {
-        const f4 mu0 = ld4(smean + c), iv0 = ld4(sinv + c), sc0 = ld4(scale + c), sf0 = ld4(shift + c);
-        const f4 mu1 = ld4(smean + C + c), iv1 = ld4(sinv + C + c), sc1 = ld4(scale + C + c), sf1 = ld4(shift + C + c);
+    if (c < w.C) {
+        SegStat s0, s1;
+        s0.load(0, c, w);
+        s1.load(1, c, w);
         for (int64_t cell = ch.beg + pl; cell < ch.end; cell += npl) {
             f4 g0[4], g1[4];
             int64_t pix[4];
@@ -640,35 +650,32 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_partial_pair(const T
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (ok[k]) {
-                    const f4 z0 = relu_mask(y0[k], sc0, sf0, g0[k]);
+                    const f4 z0 = s0.dz(y0[k], g0[k]);
                     a1 += z0;
-                    a2 += z0 * ((y0[k] - mu0) * iv0);
-                    const f4 z1 = relu_mask(y1[k], sc1, sf1, g1[k]);
+                    a2 += z0 * s0.xhat(y0[k]);
+                    const f4 z1 = s1.dz(y1[k], g1[k]);
                     b1 += z1;
-                    b2 += z1 * ((y1[k] - mu1) * iv1);
+                    b2 += z1 * s1.xhat(y1[k]);
                 }
         }
     }
-    pooled_rec2(sh1, sh2, a1, a2, tid, pl, npl, qpb, c, C, nrec, blockIdx.x, rec);
-    pooled_rec2(sh1, sh2, b1, b2, tid, pl, npl, qpb, c, C, nrec, ncps + blockIdx.x, rec);
+    const f4 a[2] = {a1, a2}, b[2] = {b1, b2};
+    block_rec<2, true>(sh, a, L, w.C, w.nrec, int(blockIdx.x), rec);
+    block_rec<2>(sh, b, L, w.C, w.nrec, w.ncps + int(blockIdx.x), rec);
 }
 
 // bn_bwd_partial over cells: rec[c][chunk][2] = {sum dz, sum dz*xhat} of the chunk's cells' pixels.
 template <class T, bool S2>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_partial(const T *__restrict__ y, int ldy, PooledCells<T> P,
-                                                                    int C, int64_t cseg, int ncps, int chunk, int nrec,
-                                                                    int qpb, const float *smean, const float *sinv,
-                                                                    const float *scale, const float *shift,
-                                                                    float *__restrict__ rec) {
-    __shared__ f4 sh1[BN_THREADS], sh2[BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
-    const Chunk ch = chunk_of(cseg, ncps, chunk);
+                                                                    BnWalk w, float *__restrict__ rec) {
+    __shared__ f4 sh[2][BN_THREADS];
+    const Lane L = lane_of(w.qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
+    const Chunk ch = chunk_of(w);
     f4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
-    if (c < C) {
-        const int o = ch.seg * C + c;
-        const f4 mu = ld4(smean + o), iv = ld4(sinv + o), sc = ld4(scale + o), sf = ld4(shift + o);
+    if (c < w.C) {
+        SegStat st;
+        st.load(ch.seg, c, w);
         for (int64_t cell = ch.beg + pl; cell < ch.end; cell += npl) {
             f4 g[4];
             int64_t pix[4];
@@ -680,58 +687,30 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_partial(const T *__r
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (ok[k]) {
-                    const f4 z = relu_mask(yv[k], sc, sf, g[k]);
+                    const f4 z = st.dz(yv[k], g[k]);
                     s1 += z;
-                    s2 += z * ((yv[k] - mu) * iv);
+                    s2 += z * st.xhat(yv[k]);
                 }
         }
     }
-    sh1[tid] = s1;
-    sh2[tid] = s2;
-    __syncthreads();
-    for (int off = npl / 2; off > 0; off >>= 1) {
-        if (pl < off) {
-            sh1[tid] += sh1[tid + off * qpb];
-            sh2[tid] += sh2[tid + off * qpb];
-        }
-        __syncthreads();
-    }
-    if (pl == 0 && c < C) {
-        const f4 a = sh1[tid], b = sh2[tid];
-        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float *r = rec + (size_t(c + k) * nrec + blockIdx.x) * 2;
-            r[0] = av[k];
-            r[1] = bv[k];
-        }
-    }
+    const f4 s[2] = {s1, s2};
+    block_rec<2>(sh, s, L, w.C, w.nrec, blockIdx.x, rec);
 }
 
 // bn_bwd_apply over cells (see bn_bwd_pooled_partial); brec[c][chunk] (conv bias grad) and dy_bound optional.
 template <class T, bool S2>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply(const T *__restrict__ y, int ldy, PooledCells<T> P,
-                                                                  T *__restrict__ dy, int lddy, int C, int64_t cseg,
-                                                                  int ncps, int chunk, int nrec, int qpb,
-                                                                  const float *smean, const float *sinv,
-                                                                  const float *gamma, const float *scale,
-                                                                  const float *shift, const float *coef,
+                                                                  T *__restrict__ dy, int lddy, BnWalk w,
                                                                   float *__restrict__ brec, float *dy_bound) {
-    __shared__ f4 sh[BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
-    const Chunk ch = chunk_of(cseg, ncps, chunk);
+    __shared__ f4 sh[1][BN_THREADS];
+    const Lane L = lane_of(w.qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
+    const Chunk ch = chunk_of(w);
     f4 acc = {0.f, 0.f, 0.f, 0.f};
     f4 amax = acc;
-    if (c < C) {
-        const int o = ch.seg * C + c;
-        const f4 mu = ld4(smean + o), iv = ld4(sinv + o), sc = ld4(scale + o), sf = ld4(shift + o);
-        const float *cf = coef + size_t(o) * 2;
-        const f4 k1 = {cf[0], cf[2], cf[4], cf[6]};
-        const f4 k2 = {cf[1], cf[3], cf[5], cf[7]};
-        const f4 gm = gamma ? ld4(gamma + c) : f4{1.f, 1.f, 1.f, 1.f};
-        const f4 mul = gm * iv;
+    if (c < w.C) {
+        SegCoef st;
+        st.load(ch.seg, c, w);
         for (int64_t cell = ch.beg + pl; cell < ch.end; cell += npl) {
             f4 g[4];
             int64_t pix[4];
@@ -743,7 +722,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply(const T *__res
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (ok[k]) {
-                    const f4 ov = stored4(dy, bn_bwd_dy4(yv[k], g[k], mu, iv, sc, sf, k1, k2, mul));
+                    const f4 ov = st.dy(dy, yv[k], g[k]);
                     st4(dy + pix[k] * lddy + c, ov);
                     acc += ov;
                     amax = fmax4(amax, fabs4(ov));
@@ -752,43 +731,28 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply(const T *__res
     }
     if (dy_bound) wave_max_bound(dy_bound, fmaxf(fmaxf(amax.x, amax.y), fmaxf(amax.z, amax.w)));
     if (!brec) return;  // uniform
-    sh[tid] = acc;
-    __syncthreads();
-    for (int off = npl / 2; off > 0; off >>= 1) {
-        if (pl < off) sh[tid] += sh[tid + off * qpb];
-        __syncthreads();
-    }
-    if (pl == 0 && c < C) {
-        const f4 a = sh[tid];
-        const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) brec[size_t(c + k) * nrec + blockIdx.x] = av[k];
-    }
+    const f4 v[1] = {acc};
+    block_rec<1>(sh, v, L, w.C, w.nrec, blockIdx.x, brec);
 }
 
 // bn_bwd_pooled_apply for a Siamese pair (see bn_bwd_pooled_partial_pair): both segments' dy per cell, the conv-bias
 // records of chunk k of each segment, bit-identical.
 template <class T, bool S2>
-__global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply_pair(
-    const T *__restrict__ y, int ldy, PooledCells<T> P, T *__restrict__ dy, int lddy, int C, int64_t cseg, int ncps,
-    int chunk, int nrec, int qpb, const float *smean, const float *sinv, const float *gamma, const float *scale,
-    const float *shift, const float *coef, float *__restrict__ brec, float *dy_bound) {
-    __shared__ f4 sh[BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
-    const Chunk ch = chunk_of(cseg, ncps, chunk);
-    const int64_t poff = int64_t(P.da.gsn) * P.da.hx * P.da.wx;
+__global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply_pair(const T *__restrict__ y, int ldy,
+                                                                       PooledCells<T> P, T *__restrict__ dy, int lddy,
+                                                                       BnWalk w, float *__restrict__ brec,
+                                                                       float *dy_bound) {
+    __shared__ f4 sh[1][BN_THREADS];
+    const Lane L = lane_of(w.qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
+    const Chunk ch = chunk_of(w);
+    const int64_t poff = int64_t(P.gsn) * P.hx * P.wx;
     f4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
     f4 amax = acc0;
-    if (c < C) {
-        const f4 gm = gamma ? ld4(gamma + c) : f4{1.f, 1.f, 1.f, 1.f};
-        const f4 mu0 = ld4(smean + c), iv0 = ld4(sinv + c), sc0 = ld4(scale + c), sf0 = ld4(shift + c);
-        const f4 mu1 = ld4(smean + C + c), iv1 = ld4(sinv + C + c), sc1 = ld4(scale + C + c), sf1 = ld4(shift + C + c);
-        const float *cf0 = coef + size_t(c) * 2, *cf1 = coef + size_t(C + c) * 2;
-        const f4 k10 = {cf0[0], cf0[2], cf0[4], cf0[6]}, k20 = {cf0[1], cf0[3], cf0[5], cf0[7]};
-        const f4 k11 = {cf1[0], cf1[2], cf1[4], cf1[6]}, k21 = {cf1[1], cf1[3], cf1[5], cf1[7]};
-        const f4 mul0 = gm * iv0, mul1 = gm * iv1;
+    if (c < w.C) {
+        SegCoef s0, s1;
+        s0.load(0, c, w);
+        s1.load(1, c, w);
         for (int64_t cell = ch.beg + pl; cell < ch.end; cell += npl) {
             f4 g0[4], g1[4];
             int64_t pix[4];
@@ -803,8 +767,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply_pair(
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (ok[k]) {
-                    const f4 o0 = stored4(dy, bn_bwd_dy4(y0[k], g0[k], mu0, iv0, sc0, sf0, k10, k20, mul0));
-                    const f4 o1 = stored4(dy, bn_bwd_dy4(y1[k], g1[k], mu1, iv1, sc1, sf1, k11, k21, mul1));
+                    const f4 o0 = s0.dy(dy, y0[k], g0[k]);
+                    const f4 o1 = s1.dy(dy, y1[k], g1[k]);
                     st4(dy + pix[k] * lddy + c, o0);
                     st4(dy + (pix[k] + poff) * lddy + c, o1);
                     acc0 += o0;
@@ -815,40 +779,29 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply_pair(
     }
     if (dy_bound) wave_max_bound(dy_bound, fmaxf(fmaxf(amax.x, amax.y), fmaxf(amax.z, amax.w)));
     if (!brec) return;  // uniform
-#pragma unroll
-    for (int sgm = 0; sgm < 2; ++sgm) {
-        sh[tid] = sgm ? acc1 : acc0;
-        __syncthreads();
-        for (int off = npl / 2; off > 0; off >>= 1) {
-            if (pl < off) sh[tid] += sh[tid + off * qpb];
-            __syncthreads();
-        }
-        if (pl == 0 && c < C) {
-            const f4 a = sh[tid];
-            const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) brec[size_t(c + k) * nrec + sgm * ncps + blockIdx.x] = av[k];
-        }
-        __syncthreads();
-    }
+    const f4 v0[1] = {acc0}, v1[1] = {acc1};
+    block_rec<1, true>(sh, v0, L, w.C, w.nrec, int(blockIdx.x), brec);
+    block_rec<1>(sh, v1, L, w.C, w.nrec, w.ncps + int(blockIdx.x), brec);
 }
 
 // per (chunk) record {sum dz, sum dz*xhat}, rec[c][chunk][2]
+// The two pixel-walk partial kernels take the walk's fields as separate arguments, not as a BnWalk: with the block
+// among the kernel arguments hipcc waited for the DaHeadN<2> walk's eight gradient loads before it issued the four y
+// loads (two memory latencies per trip).
 template <class T, class DA>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_partial(const T *__restrict__ y, int ldy, DA da, int C,
                                                              int64_t pseg, int ncps, int chunk, int nrec, int qpb,
                                                              const float *smean, const float *sinv, const float *scale,
                                                              const float *shift, float *__restrict__ rec) {
-    __shared__ f4 sh1[BN_THREADS], sh2[BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
+    __shared__ f4 sh[2][BN_THREADS];
+    const Lane L = lane_of(qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
     const Chunk ch = chunk_of(pseg, ncps, chunk);
     f4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
     da.bind(c);
     if (c < C) {
-        const int o = ch.seg * C + c;
-        const f4 mu = ld4(smean + o), iv = ld4(sinv + o), sc = ld4(scale + o), sf = ld4(shift + o);
+        SegStat st;
+        st.load(ch.seg * C + c, smean, sinv, scale, shift);
         int64_t p = ch.beg + pl;
         for (; p + 3 * npl < ch.end; p += 4 * npl) {
             f4 y0 = ld4(y + p * ldy + c), y1 = ld4(y + (p + npl) * ldy + c);
@@ -857,38 +810,19 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_partial(const T *__restrict
             f4 g2 = da(p + 2 * npl, c), g3 = da(p + 3 * npl, c);
             PIN4(y0, y1, y2, y3);
             PIN4(g0, g1, g2, g3);
-            const f4 z0 = relu_mask(y0, sc, sf, g0), z1 = relu_mask(y1, sc, sf, g1);
-            const f4 z2 = relu_mask(y2, sc, sf, g2), z3 = relu_mask(y3, sc, sf, g3);
+            const f4 z0 = st.dz(y0, g0), z1 = st.dz(y1, g1), z2 = st.dz(y2, g2), z3 = st.dz(y3, g3);
             s1 += (z0 + z1) + (z2 + z3);
-            s2 += (z0 * ((y0 - mu) * iv) + z1 * ((y1 - mu) * iv)) + (z2 * ((y2 - mu) * iv) + z3 * ((y3 - mu) * iv));
+            s2 += (z0 * st.xhat(y0) + z1 * st.xhat(y1)) + (z2 * st.xhat(y2) + z3 * st.xhat(y3));
         }
         for (; p < ch.end; p += npl) {
             const f4 y0 = ld4(y + p * ldy + c);
-            const f4 z0 = relu_mask(y0, sc, sf, da(p, c));
+            const f4 z0 = st.dz(y0, da(p, c));
             s1 += z0;
-            s2 += z0 * ((y0 - mu) * iv);
+            s2 += z0 * st.xhat(y0);
         }
     }
-    sh1[tid] = s1;
-    sh2[tid] = s2;
-    __syncthreads();
-    for (int off = npl / 2; off > 0; off >>= 1) {
-        if (pl < off) {
-            sh1[tid] += sh1[tid + off * qpb];
-            sh2[tid] += sh2[tid + off * qpb];
-        }
-        __syncthreads();
-    }
-    if (pl == 0 && c < C) {
-        const f4 a = sh1[tid], b = sh2[tid];
-        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float *r = rec + (size_t(c + k) * nrec + blockIdx.x) * 2;
-            r[0] = av[k];
-            r[1] = bv[k];
-        }
-    }
+    const f4 s[2] = {s1, s2};
+    block_rec<2>(sh, s, L, C, nrec, blockIdx.x, rec);
 }
 
 // bn_bwd_partial for the head's BatchNorm (DaHead) that also takes the 1x1 head's weight grad from the same pass:
@@ -901,23 +835,24 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_partial_head(const T *__res
                                                                   const float *smean, const float *sinv,
                                                                   const float *scale, const float *shift,
                                                                   float *__restrict__ rec, float *__restrict__ hrec) {
-    __shared__ f4 sh1[BN_THREADS], sh2[BN_THREADS], shh[NO][BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
+    __shared__ f4 sh[2 + NO][BN_THREADS];
+    const Lane L = lane_of(qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
     const Chunk ch = chunk_of(pseg, ncps, chunk);
     const f4 zero = {0.f, 0.f, 0.f, 0.f};
+    // {sum dz, sum dz*xhat} and the NO weight-grad sums; one array of all 2 + NO split the twelve loads of a
+    // <float, 2> trip over three waits
     f4 s1 = zero, s2 = zero, hw[NO];
 #pragma unroll
     for (int k = 0; k < NO; ++k) hw[k] = zero;
     if (c < C) {
-        const int o = ch.seg * C + c;
-        const f4 mu = ld4(smean + o), iv = ld4(sinv + o), sc = ld4(scale + o), sf = ld4(shift + o);
+        SegStat st;
+        st.load(ch.seg * C + c, smean, sinv, scale, shift);
         f4 w4[NO];
 #pragma unroll
         for (int k = 0; k < NO; ++k) w4[k] = ld4(da.w + int64_t(k) * C + c);
-        // one pixel: its n_out gradient values, dL/da (DaHead's fma chain) and the activation
-        auto px = [&](int64_t p, f4 yv, f4 (&gk)[NO]) {
+        // one pixel: its n_out gradient values and dL/da (DaHeadN's fma chain)
+        auto px = [&](int64_t p, f4 (&gk)[NO]) {
             const uint32_t img = fdiv(uint32_t(p), da.div_hw);
             const int pix = int(uint32_t(p) - img * uint32_t(da.hw));
             float gv[NO];
@@ -939,60 +874,37 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_partial_head(const T *__res
             f4 y0 = ld4(y + p * ldy + c), y1 = ld4(y + (p + npl) * ldy + c);
             f4 y2 = ld4(y + (p + 2 * npl) * ldy + c), y3 = ld4(y + (p + 3 * npl) * ldy + c);
             f4 k0[NO], k1[NO], k2[NO], k3[NO];
-            f4 g0 = px(p, y0, k0), g1 = px(p + npl, y1, k1);
-            f4 g2 = px(p + 2 * npl, y2, k2), g3 = px(p + 3 * npl, y3, k3);
+            f4 g0 = px(p, k0), g1 = px(p + npl, k1);
+            f4 g2 = px(p + 2 * npl, k2), g3 = px(p + 3 * npl, k3);
             PIN4(y0, y1, y2, y3);
             PIN4(g0, g1, g2, g3);
-            const f4 z0 = relu_mask(y0, sc, sf, g0), z1 = relu_mask(y1, sc, sf, g1);
-            const f4 z2 = relu_mask(y2, sc, sf, g2), z3 = relu_mask(y3, sc, sf, g3);
+            const f4 z0 = st.dz(y0, g0), z1 = st.dz(y1, g1), z2 = st.dz(y2, g2), z3 = st.dz(y3, g3);
             s1 += (z0 + z1) + (z2 + z3);
-            s2 += (z0 * ((y0 - mu) * iv) + z1 * ((y1 - mu) * iv)) + (z2 * ((y2 - mu) * iv) + z3 * ((y3 - mu) * iv));
-            const f4 a0 = bn_relu4(y0, sc, sf), a1 = bn_relu4(y1, sc, sf);
-            const f4 a2 = bn_relu4(y2, sc, sf), a3 = bn_relu4(y3, sc, sf);
+            s2 += (z0 * st.xhat(y0) + z1 * st.xhat(y1)) + (z2 * st.xhat(y2) + z3 * st.xhat(y3));
+            const f4 a0 = bn_relu4(y0, st.sc, st.sf), a1 = bn_relu4(y1, st.sc, st.sf);
+            const f4 a2 = bn_relu4(y2, st.sc, st.sf), a3 = bn_relu4(y3, st.sc, st.sf);
 #pragma unroll
             for (int k = 0; k < NO; ++k) hw[k] += (a0 * k0[k] + a1 * k1[k]) + (a2 * k2[k] + a3 * k3[k]);
         }
         for (; p < ch.end; p += npl) {
             const f4 y0 = ld4(y + p * ldy + c);
             f4 k0[NO];
-            const f4 z0 = relu_mask(y0, sc, sf, px(p, y0, k0));
+            const f4 z0 = st.dz(y0, px(p, k0));
             s1 += z0;
-            s2 += z0 * ((y0 - mu) * iv);
-            const f4 a0 = bn_relu4(y0, sc, sf);
+            s2 += z0 * st.xhat(y0);
+            const f4 a0 = bn_relu4(y0, st.sc, st.sf);
 #pragma unroll
             for (int k = 0; k < NO; ++k) hw[k] += a0 * k0[k];
         }
     }
-    sh1[tid] = s1;
-    sh2[tid] = s2;
+    f4 s[2 + NO] = {s1, s2};
 #pragma unroll
-    for (int k = 0; k < NO; ++k) shh[k][tid] = hw[k];
-    __syncthreads();
-    for (int off = npl / 2; off > 0; off >>= 1) {
-        if (pl < off) {
-            sh1[tid] += sh1[tid + off * qpb];
-            sh2[tid] += sh2[tid + off * qpb];
-#pragma unroll
-            for (int k = 0; k < NO; ++k) shh[k][tid] += shh[k][tid + off * qpb];
-        }
-        __syncthreads();
-    }
+    for (int k = 0; k < NO; ++k) s[2 + k] = hw[k];
+    block_tree_sum(sh, s, L);
     if (pl == 0 && c < C) {
-        const f4 a = sh1[tid], b = sh2[tid];
-        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+        store_rec<2>(sh, c, nrec, blockIdx.x, rec);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float *r = rec + (size_t(c + k) * nrec + blockIdx.x) * 2;
-            r[0] = av[k];
-            r[1] = bv[k];
-        }
-#pragma unroll
-        for (int o = 0; o < NO; ++o) {
-            const f4 h = shh[o][tid];
-            const float hv[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) hrec[(size_t(o) * C + c + k) * nrec + blockIdx.x] = hv[k];
-        }
+        for (int o = 0; o < NO; ++o) store_rec<1>(sh + 2 + o, c, nrec, blockIdx.x, hrec + size_t(o) * C * nrec);
     }
 }
 
@@ -1011,11 +923,9 @@ __device__ __forceinline__ float bn_dy_bound(double da_bound, double n, double g
 // sum_seg gamma*invstd * (S1 - pseg * k1) -- zero but for the rounding of k1, as BatchNorm removes the mean.
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalize(const float *__restrict__ rec, int C, int nseg,
                                                               int ncps, int nrec, int64_t pseg, float *coef,
-                                                              float *dgamma, float *dbeta, const float *gamma = nullptr,
-                                                              const float *sinv = nullptr, float *dbias = nullptr,
-                                                              const float *smean = nullptr,
-                                                              const float *da_bound = nullptr,
-                                                              float *dy_bound = nullptr) {
+                                                              float *dgamma, float *dbeta, const float *gamma,
+                                                              const float *sinv, float *dbias, const float *smean,
+                                                              const float *da_bound, float *dy_bound) {
     __shared__ double a1[BN_THREADS], a2[BN_THREADS];
     const int c = blockIdx.x;
     const int t = threadIdx.x;
@@ -1083,27 +993,18 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalize(const float *__res
 // dy = gamma*invstd*(dz - k1 - xhat*k2); optional per-chunk sums of dy (conv bias grad), brec[c][chunk]
 template <class T, class DA>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply(const T *__restrict__ y, int ldy, DA da,
-                                                           T *__restrict__ dy, int lddy, int C, int64_t pseg,
-                                                           int ncps, int chunk, int nrec, int qpb, const float *smean,
-                                                           const float *sinv, const float *gamma, const float *scale,
-                                                           const float *shift, const float *coef,
+                                                           T *__restrict__ dy, int lddy, BnWalk w,
                                                            float *__restrict__ brec, float *dy_bound) {
-    __shared__ f4 sh[BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
-    const Chunk ch = chunk_of(pseg, ncps, chunk);
+    __shared__ f4 sh[1][BN_THREADS];
+    const Lane L = lane_of(w.qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
+    const Chunk ch = chunk_of(w);
     f4 acc = {0.f, 0.f, 0.f, 0.f};
     f4 amax = acc;  // max |dy| of this thread (dy_bound)
     da.bind(c);
-    if (c < C) {
-        const int o = ch.seg * C + c;
-        const f4 mu = ld4(smean + o), iv = ld4(sinv + o), sc = ld4(scale + o), sf = ld4(shift + o);
-        const float *cf = coef + size_t(o) * 2;
-        const f4 k1 = {cf[0], cf[2], cf[4], cf[6]};
-        const f4 k2 = {cf[1], cf[3], cf[5], cf[7]};
-        const f4 gm = gamma ? ld4(gamma + c) : f4{1.f, 1.f, 1.f, 1.f};
-        const f4 mul = gm * iv;
+    if (c < w.C) {
+        SegCoef st;
+        st.load(ch.seg, c, w);
         int64_t p = ch.beg + pl;
         for (; p + 3 * npl < ch.end; p += 4 * npl) {
             f4 y0 = ld4(y + p * ldy + c), y1 = ld4(y + (p + npl) * ldy + c);
@@ -1112,10 +1013,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply(const T *__restrict__
             f4 g2 = da(p + 2 * npl, c), g3 = da(p + 3 * npl, c);
             PIN4(y0, y1, y2, y3);
             PIN4(g0, g1, g2, g3);
-            const f4 o0 = stored4(dy, bn_bwd_dy4(y0, g0, mu, iv, sc, sf, k1, k2, mul));
-            const f4 o1 = stored4(dy, bn_bwd_dy4(y1, g1, mu, iv, sc, sf, k1, k2, mul));
-            const f4 o2 = stored4(dy, bn_bwd_dy4(y2, g2, mu, iv, sc, sf, k1, k2, mul));
-            const f4 o3 = stored4(dy, bn_bwd_dy4(y3, g3, mu, iv, sc, sf, k1, k2, mul));
+            const f4 o0 = st.dy(dy, y0, g0), o1 = st.dy(dy, y1, g1), o2 = st.dy(dy, y2, g2), o3 = st.dy(dy, y3, g3);
             st4(dy + p * lddy + c, o0);
             st4(dy + (p + npl) * lddy + c, o1);
             st4(dy + (p + 2 * npl) * lddy + c, o2);
@@ -1125,7 +1023,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply(const T *__restrict__
         }
         for (; p < ch.end; p += npl) {
             const f4 y0 = ld4(y + p * ldy + c);
-            const f4 o0 = stored4(dy, bn_bwd_dy4(y0, da(p, c), mu, iv, sc, sf, k1, k2, mul));
+            const f4 o0 = st.dy(dy, y0, da(p, c));
             st4(dy + p * lddy + c, o0);
             acc += o0;
             if (dy_bound) amax = fmax4(amax, fabs4(o0));
@@ -1133,18 +1031,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply(const T *__restrict__
     }
     if (dy_bound) wave_max_bound(dy_bound, fmaxf(fmaxf(amax.x, amax.y), fmaxf(amax.z, amax.w)));
     if (!brec) return;  // uniform
-    sh[tid] = acc;
-    __syncthreads();
-    for (int off = npl / 2; off > 0; off >>= 1) {
-        if (pl < off) sh[tid] += sh[tid + off * qpb];
-        __syncthreads();
-    }
-    if (pl == 0 && c < C) {
-        const f4 a = sh[tid];
-        const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) brec[size_t(c + k) * nrec + blockIdx.x] = av[k];
-    }
+    const f4 v[1] = {acc};
+    block_rec<1>(sh, v, L, w.C, w.nrec, blockIdx.x, brec);
 }
 
 // out[c] = sum_r rec[c][r] (double, fixed tree); one workgroup per channel
@@ -1175,10 +1063,9 @@ __global__ __launch_bounds__(BN_THREADS) void chan_sum_partial(const T *__restri
                                                                int o, const float *__restrict__ scale,
                                                                const float *__restrict__ shift, int64_t pseg,
                                                                float *__restrict__ rec) {
-    __shared__ f4 sh[BN_THREADS];
-    const int tid = threadIdx.x;
-    const int q = tid % qpb, pl = tid / qpb, npl = BN_THREADS / qpb;
-    const int c = (blockIdx.y * qpb + q) * 4;
+    __shared__ f4 sh[1][BN_THREADS];
+    const Lane L = lane_of(qpb);
+    const int c = L.c, pl = L.pl, npl = L.npl;
     const int64_t pbeg = int64_t(blockIdx.x) * chunk;
     const int64_t pend = min(pbeg + chunk, npix);
     f4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -1222,18 +1109,8 @@ __global__ __launch_bounds__(BN_THREADS) void chan_sum_partial(const T *__restri
         }
         for (; p < pend; p += npl) acc += value(p, ld4(x + p * ldx + c), wgt ? wgt_at(p) : 1.f);
     }
-    sh[tid] = acc;
-    __syncthreads();
-    for (int off = npl / 2; off > 0; off >>= 1) {
-        if (pl < off) sh[tid] += sh[tid + off * qpb];
-        __syncthreads();
-    }
-    if (pl == 0 && c < C) {
-        const f4 a = sh[tid];
-        const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) rec[size_t(c + k) * nrec + blockIdx.x] = av[k];
-    }
+    const f4 v[1] = {acc};
+    block_rec<1>(sh, v, L, C, nrec, blockIdx.x, rec);
 }
 
 static int bn_check(const scd_nhwc_t &y, int nseg) {
@@ -1250,10 +1127,6 @@ size_t weighted_channel_sum_bytes(const scd_nhwc_t &x) {
     const BnGeom g = bn_geom(x, 1);
     return size_t(g.nrec) * x.c * sizeof(float);
 }
-
-int weighted_channel_sum(const scd_nhwc_t &x, const float *wgt, int n_out, int o, float *out, void *ws,
-                         size_t ws_bytes, hipStream_t s, const float *scale = nullptr, const float *shift = nullptr,
-                         int nseg = 1);
 
 // scale / shift (optional, per segment of nseg): sum relu(fma(x, scale, shift)) instead of x.
 int weighted_channel_sum(const scd_nhwc_t &x, const float *wgt, int n_out, int o, float *out, void *ws,
@@ -1392,133 +1265,168 @@ extern "C" int scd_bn_relu_apply(scd_nhwc_t y, int32_t nseg, const float *scale,
 }
 
 namespace scd {
-// partial -> finalize -> apply (+ conv-bias sums) over a gradient source DA
-template <class T, class DA>
-static void bn_backward_run(const scd_nhwc_t &y, DA da, int nseg, const float *save_mean, const float *save_invstd,
-                            const float *gamma, const float *scale, const float *shift, float *dgamma, float *dbeta,
-                            float *dbias_prev, const scd_nhwc_t &dy, float *dy_bound, void *ws, hipStream_t s) {
-    const BnGeom g = bn_geom(y, nseg);
-    float *rec = static_cast<float *>(ws);
-    float *brec = rec + size_t(g.nrec) * y.c * 2;
-    float *coef = brec + size_t(g.nrec) * y.c;
-    hipLaunchKernelGGL((bn_bwd_partial<T, DA>), dim3(g.nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                       view_ptr<const T>(y), y.ldc, da, y.c, g.pseg, g.ncps, g.chunk, g.nrec, g.qpb,
-                       save_mean, save_invstd, scale, shift, rec);
-    hipLaunchKernelGGL(bn_bwd_finalize, dim3(y.c), dim3(BN_THREADS), 0, s, rec, y.c, nseg, g.ncps, g.nrec, g.pseg,
-                       coef, dgamma, dbeta);
-    hipLaunchKernelGGL((bn_bwd_apply<T, DA>), dim3(g.nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                       view_ptr<const T>(y), y.ldc, da, view_ptr<T>(dy), dy.ldc, y.c,
-                       g.pseg, g.ncps, g.chunk, g.nrec, g.qpb, save_mean, save_invstd, gamma, scale, shift, coef,
-                       dbias_prev ? brec : nullptr, dy_bound);
-    if (dbias_prev) hipLaunchKernelGGL(sum_records, dim3(y.c), dim3(BN_THREADS), 0, s, brec, g.nrec, dbias_prev);
-}
-// The head's BatchNorm backward (DaHead) with the head's weight grad from the same partial pass (w_grad non-null):
-// hrec after the usual records (scd_bn_head_workspace_bytes).
-template <class T, int NO>
-static void bn_backward_run_head(const scd_nhwc_t &y, const DaHead &da, int nseg, const float *save_mean,
-                                 const float *save_invstd, const float *gamma, const float *scale, const float *shift,
-                                 float *dgamma, float *dbeta, float *dbias_prev, const scd_nhwc_t &dy, float *dy_bound,
-                                 float *w_grad, void *ws, hipStream_t s) {
-    const BnGeom g = bn_geom(y, nseg);
-    float *rec = static_cast<float *>(ws);
-    float *brec = rec + size_t(g.nrec) * y.c * 2;
-    float *coef = brec + size_t(g.nrec) * y.c;
-    float *hrec = reinterpret_cast<float *>(static_cast<unsigned char *>(ws) +
-                                            scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, nseg));
-    hipLaunchKernelGGL((bn_bwd_partial_head<T, NO>), dim3(g.nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                       view_ptr<const T>(y), y.ldc, da, y.c, g.pseg, g.ncps, g.chunk, g.nrec, g.qpb,
-                       save_mean, save_invstd, scale, shift, rec, hrec);
-    hipLaunchKernelGGL(bn_bwd_finalize, dim3(y.c), dim3(BN_THREADS), 0, s, rec, y.c, nseg, g.ncps, g.nrec, g.pseg,
-                       coef, dgamma, dbeta);
-    hipLaunchKernelGGL((bn_bwd_apply<T, DaHeadN<NO>>), dim3(g.nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                       view_ptr<const T>(y), y.ldc, DaHeadN<NO>{da, {}}, view_ptr<T>(dy), dy.ldc, y.c,
-                       g.pseg, g.ncps, g.chunk, g.nrec, g.qpb, save_mean, save_invstd, gamma, scale, shift, coef,
-                       dbias_prev ? brec : nullptr, dy_bound);
-    if (dbias_prev) hipLaunchKernelGGL(sum_records, dim3(y.c), dim3(BN_THREADS), 0, s, brec, g.nrec, dbias_prev);
-    hipLaunchKernelGGL(sum_records, dim3(da.n_out * y.c), dim3(BN_THREADS), 0, s, hrec, g.nrec, w_grad);
-}
-// The encoder levels' BatchNorm backward with the pooled gradient (DaPooled) over 2x2 cells.  The chunks partition
-// each segment's cells into at most bn_geom's chunk count, so the records fit the same workspace.
-// Building with -DSCD_BN_POOLED_CELLS=0 runs the per-pixel kernels instead (A/B experiments; bit-identical).
-#ifndef SCD_BN_POOLED_CELLS
-#define SCD_BN_POOLED_CELLS 1
-#endif
-#ifndef SCD_BN_POOLED_PAIR
-#define SCD_BN_POOLED_PAIR 1
-#endif
-template <class T, bool S2>
-static void bn_backward_pooled_cells(const scd_nhwc_t &y, const PooledCells<T> &P, int nseg, const BnGeom &g,
-                                     int64_t cseg, int chunk, int ncps, int nrec, const float *save_mean,
-                                     const float *save_invstd, const float *gamma, const float *scale,
-                                     const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
-                                     const scd_nhwc_t &dy, float *dy_bound, float *rec, float *brec, float *coef,
-                                     hipStream_t s);
-template <class T>
-static void bn_backward_run_pooled(const scd_nhwc_t &y, const DaPooled<T> &da, int nseg, const float *save_mean,
-                                   const float *save_invstd, const float *gamma, const float *scale, const float *shift,
-                                   float *dgamma, float *dbeta, float *dbias_prev, const scd_nhwc_t &dy,
-                                   float *dy_bound, void *ws, hipStream_t s) {
-    if (!SCD_BN_POOLED_CELLS) {
-        bn_backward_run<T>(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy,
-                           dy_bound, ws, s);
-        return;
+// What every form of the BatchNorm + ReLU backward shares: the entry points' common arguments as they received them,
+// then what bn_bwd_check derives from them.
+struct BnBwd {
+    scd_nhwc_t y;
+    int nseg;
+    const float *save_mean, *save_invstd, *gamma, *scale, *shift;
+    float *dgamma, *dbeta, *dbias_prev;
+    scd_nhwc_t dy;  // none in the coefficient-only form
+    float *dy_bound;
+    void *ws;
+    size_t ws_bytes;
+    hipStream_t s;
+    // bn_bwd_check: the pixel walk's geometry and the workspace, carved into rec[c][nrec][2], brec[c][nrec] and
+    // coef[seg][c][2]
+    BnGeom g;
+    float *rec, *brec, *coef;
+
+    // the kernels' parameter block for a walk over segments of lseg pixels (or cells) in ncps chunks of `chunk`
+    BnWalk walk(int64_t lseg, int chunk, int ncps) const {
+        return BnWalk{y.c, lseg, ncps, chunk, nseg * ncps, g.qpb, save_mean, save_invstd, gamma, scale, shift, coef};
     }
-    const BnGeom g = bn_geom(y, nseg);
-    PooledCells<T> P;
-    P.da = da;
+    BnWalk pixel_walk() const { return walk(g.pseg, g.chunk, g.ncps); }
+};
+
+struct BnView {
+    const scd_nhwc_t *v;
+    const char *name;
+    bool optional, like_y;  // may be null / has y's shape
+};
+
+// The checks of the backward entry points `who`, in the order they always had: y and nseg, the views (all of them,
+// then their shapes), the coefficient arrays, what `more` adds (SCD_OK, or an error set and its code), the workspace
+// (`need` bytes; 0: scd_bn_workspace_bytes).  Then the workspace is carved.
+template <class More>
+static int bn_bwd_check(const char *who, BnBwd &b, std::initializer_list<BnView> views, size_t need, More more) {
+    const scd_nhwc_t &y = b.y;
+    SCD_TRY(bn_check(y, b.nseg));
+    for (const BnView &v : views) SCD_TRY(check_view(*v.v, v.name, v.optional));
+    bool bad = !b.save_mean || !b.save_invstd || !b.scale || !b.shift;
+    for (const BnView &v : views)
+        bad |= v.like_y && (v.v->n != y.n || v.v->h != y.h || v.v->w != y.w || v.v->c != y.c);
+    if (bad) {
+        set_error("%s: shape mismatch / null", who);
+        return SCD_ERR_ARG;
+    }
+    SCD_TRY(more());
+    if (!need) need = scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, b.nseg);
+    if (!b.ws || b.ws_bytes < need) {
+        set_error("%s: workspace %zu < %zu bytes", who, b.ws_bytes, need);
+        return SCD_ERR_WORKSPACE;
+    }
+    b.g = bn_geom(y, b.nseg);
+    b.rec = static_cast<float *>(b.ws);
+    b.brec = b.rec + size_t(b.g.nrec) * y.c * 2;
+    b.coef = b.brec + size_t(b.g.nrec) * y.c;
+    return SCD_OK;
+}
+
+static int bn_bwd_check(const char *who, BnBwd &b, std::initializer_list<BnView> views) {
+    return bn_bwd_check(who, b, views, 0, [] { return SCD_OK; });
+}
+
+// The records bn_bwd_finalize merges (ncps per segment, nrec per channel): a partial pass' over walk w in the
+// workspace, or the tile records of the producing conv's epilogue, given by the caller.
+struct BnRecs {
+    const float *rec;
+    int ncps, nrec;
+};
+static BnRecs walk_recs(const BnBwd &b, const BnWalk &w) { return BnRecs{b.rec, w.ncps, w.nrec}; }
+static BnRecs tile_recs(const BnBwd &b, const float *tile_rec, int ntiles) {
+    return BnRecs{tile_rec, ntiles / b.nseg, ntiles};
+}
+struct NoStep {};  // the step a form does not have
+
+// The sequence of every form: partial() (records r), finalize, apply(brec) (dy, and the conv-bias records of walk w
+// when brec is not null), the conv-bias sum.
+//   partial NoStep: r are the caller's tile records;
+//   apply NoStep:   dy is formed by its consumer, so finalize also gives the conv-bias grad and raises dy_bound from
+//                   da_bound (see bn_bwd_finalize).
+template <class Partial, class Apply>
+static void bn_bwd_run(const BnBwd &b, const BnWalk &w, BnRecs r, Partial partial, Apply apply,
+                       const float *da_bound = nullptr) {
+    constexpr bool deferred = std::is_same_v<Apply, NoStep>;
+    if constexpr (!std::is_same_v<Partial, NoStep>) partial();
+    hipLaunchKernelGGL(bn_bwd_finalize, dim3(b.y.c), dim3(BN_THREADS), 0, b.s, r.rec, b.y.c, b.nseg, r.ncps, r.nrec,
+                       b.g.pseg, b.coef, b.dgamma, b.dbeta, b.gamma, b.save_invstd, deferred ? b.dbias_prev : nullptr,
+                       b.save_mean, da_bound, deferred ? b.dy_bound : nullptr);
+    if constexpr (!deferred) {
+        apply(b.dbias_prev ? b.brec : nullptr);
+        if (b.dbias_prev)
+            hipLaunchKernelGGL(sum_records, dim3(b.y.c), dim3(BN_THREADS), 0, b.s, b.brec, w.nrec, b.dbias_prev);
+    }
+}
+
+// The two steps of the pixel walk w over a gradient source DA.
+template <class T, class DA>
+static auto pixel_partial(const BnBwd &b, const BnWalk &w, DA da) {
+    return [b, w, da] {
+        hipLaunchKernelGGL((bn_bwd_partial<T, DA>), dim3(w.nrec, b.g.cgroups), dim3(BN_THREADS), 0, b.s,
+                           view_ptr<const T>(b.y), b.y.ldc, da, w.C, w.lseg, w.ncps, w.chunk, w.nrec, w.qpb, w.smean,
+                           w.sinv, w.scale, w.shift, b.rec);
+    };
+}
+template <class T, class DA>
+static auto pixel_apply(const BnBwd &b, const BnWalk &w, DA da) {
+    return [b, w, da](float *brec) {
+        hipLaunchKernelGGL((bn_bwd_apply<T, DA>), dim3(w.nrec, b.g.cgroups), dim3(BN_THREADS), 0, b.s,
+                           view_ptr<const T>(b.y), b.y.ldc, da, view_ptr<T>(b.dy), b.dy.ldc, w, brec, b.dy_bound);
+    };
+}
+
+template <class T, class DA>
+static void bn_backward_run(const BnBwd &b, DA da) {
+    const BnWalk w = b.pixel_walk();
+    bn_bwd_run(b, w, walk_recs(b, w), pixel_partial<T>(b, w, da), pixel_apply<T>(b, w, da));
+}
+
+// The head's BatchNorm backward (DaHead) with the head's weight grad from the same partial pass: hrec after the usual
+// records (scd_bn_head_workspace_bytes).
+template <class T, int NO>
+static void bn_backward_run_head(const BnBwd &b, const DaHead &da, float *w_grad) {
+    const scd_nhwc_t &y = b.y;
+    const BnWalk w = b.pixel_walk();
+    float *hrec = reinterpret_cast<float *>(static_cast<unsigned char *>(b.ws) +
+                                            scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, b.nseg));
+    bn_bwd_run(b, w, walk_recs(b, w),
+               [&] {
+                   hipLaunchKernelGGL((bn_bwd_partial_head<T, NO>), dim3(w.nrec, b.g.cgroups), dim3(BN_THREADS), 0, b.s,
+                                      view_ptr<const T>(y), y.ldc, da, w.C, w.lseg, w.ncps, w.chunk, w.nrec, w.qpb,
+                                      w.smean, w.sinv, w.scale, w.shift, b.rec, hrec);
+               },
+               pixel_apply<T>(b, w, DaHeadN<NO>{da, {}}));
+    hipLaunchKernelGGL(sum_records, dim3(da.n_out * y.c), dim3(BN_THREADS), 0, b.s, hrec, w.nrec, w_grad);
+}
+
+// The encoder levels' BatchNorm backward with the pooled gradient over 2x2 cells (P: all but the cell geometry set).
+// The chunks partition each segment's cells into at most bn_geom's chunk count, so the records fit the same workspace.
+template <class T, bool S2>
+static void bn_backward_run_pooled(const BnBwd &b, PooledCells<T> P) {
+    const scd_nhwc_t &y = b.y;
     P.ch = (y.h + 1) / 2;
     P.cw = (y.w + 1) / 2;
     P.div_cimg = make_fastdiv(uint32_t(P.ch * P.cw));
     P.div_cw = make_fastdiv(uint32_t(P.cw));
-    const int64_t cseg = int64_t(y.n / nseg) * P.ch * P.cw;
-    const int chunk = int((cseg + g.ncps - 1) / g.ncps);
-    const int ncps = int((cseg + chunk - 1) / chunk);
-    const int nrec = nseg * ncps;
-    float *rec = static_cast<float *>(ws);
-    float *brec = rec + size_t(g.nrec) * y.c * 2;
-    float *coef = brec + size_t(g.nrec) * y.c;
-    // Siamese pairs (-DSCD_BN_POOLED_PAIR=0: one image per cell walk): the t1 and t2 cells at one place in one block,
-    // the shared difference gradient read once instead of once per branch
-    if (da.gs2) {
-        bn_backward_pooled_cells<T, true>(y, P, nseg, g, cseg, chunk, ncps, nrec, save_mean, save_invstd, gamma, scale,
-                                          shift, dgamma, dbeta, dbias_prev, dy, dy_bound, rec, brec, coef, s);
-    } else {
-        bn_backward_pooled_cells<T, false>(y, P, nseg, g, cseg, chunk, ncps, nrec, save_mean, save_invstd, gamma, scale,
-                                           shift, dgamma, dbeta, dbias_prev, dy, dy_bound, rec, brec, coef, s);
-    }
-}
-
-template <class T, bool S2>
-static void bn_backward_pooled_cells(const scd_nhwc_t &y, const PooledCells<T> &P, int nseg, const BnGeom &g,
-                                     int64_t cseg, int chunk, int ncps, int nrec, const float *save_mean,
-                                     const float *save_invstd, const float *gamma, const float *scale,
-                                     const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
-                                     const scd_nhwc_t &dy, float *dy_bound, float *rec, float *brec, float *coef,
-                                     hipStream_t s) {
-    const DaPooled<T> &da = P.da;
-    if (SCD_BN_POOLED_PAIR && nseg == 2 && da.gs && (da.skip_mode == 1 || da.skip_mode == 2) && 2 * da.gsn == y.n) {
-        hipLaunchKernelGGL((bn_bwd_pooled_partial_pair<T, S2>), dim3(ncps, g.cgroups), dim3(BN_THREADS), 0, s,
-                           view_ptr<const T>(y), y.ldc, P, y.c, cseg, ncps, chunk, nrec, g.qpb, save_mean,
-                           save_invstd, scale, shift, rec);
-        hipLaunchKernelGGL(bn_bwd_finalize, dim3(y.c), dim3(BN_THREADS), 0, s, rec, y.c, nseg, ncps, nrec, g.pseg,
-                           coef, dgamma, dbeta);
-        hipLaunchKernelGGL((bn_bwd_pooled_apply_pair<T, S2>), dim3(ncps, g.cgroups), dim3(BN_THREADS), 0, s,
-                           view_ptr<const T>(y), y.ldc, P, view_ptr<T>(dy), dy.ldc, y.c,
-                           cseg, ncps, chunk, nrec, g.qpb, save_mean, save_invstd, gamma, scale, shift, coef,
-                           dbias_prev ? brec : nullptr, dy_bound);
-        if (dbias_prev) hipLaunchKernelGGL(sum_records, dim3(y.c), dim3(BN_THREADS), 0, s, brec, nrec, dbias_prev);
-        return;
-    }
-    hipLaunchKernelGGL((bn_bwd_pooled_partial<T, S2>), dim3(nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                       view_ptr<const T>(y), y.ldc, P, y.c, cseg, ncps, chunk, nrec, g.qpb, save_mean,
-                       save_invstd, scale, shift, rec);
-    hipLaunchKernelGGL(bn_bwd_finalize, dim3(y.c), dim3(BN_THREADS), 0, s, rec, y.c, nseg, ncps, nrec, g.pseg, coef,
-                       dgamma, dbeta);
-    hipLaunchKernelGGL((bn_bwd_pooled_apply<T, S2>), dim3(nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                       view_ptr<const T>(y), y.ldc, P, view_ptr<T>(dy), dy.ldc, y.c, cseg,
-                       ncps, chunk, nrec, g.qpb, save_mean, save_invstd, gamma, scale, shift, coef,
-                       dbias_prev ? brec : nullptr, dy_bound);
-    if (dbias_prev) hipLaunchKernelGGL(sum_records, dim3(y.c), dim3(BN_THREADS), 0, s, brec, nrec, dbias_prev);
+    const int64_t cseg = int64_t(y.n / b.nseg) * P.ch * P.cw;
+    const int chunk = int((cseg + b.g.ncps - 1) / b.g.ncps);
+    const BnWalk w = b.walk(cseg, chunk, int((cseg + chunk - 1) / chunk));
+    // Siamese pairs: the t1 and t2 cells at one place in one block (block k: chunk k of both segments), the shared
+    // difference gradient read once instead of once per branch
+    const bool pair = b.nseg == 2 && P.gs && (P.skip_mode == 1 || P.skip_mode == 2) && 2 * P.gsn == y.n;
+    const auto partial = pair ? bn_bwd_pooled_partial_pair<T, S2> : bn_bwd_pooled_partial<T, S2>;
+    const auto apply = pair ? bn_bwd_pooled_apply_pair<T, S2> : bn_bwd_pooled_apply<T, S2>;
+    const dim3 grid(pair ? w.ncps : w.nrec, b.g.cgroups);
+    bn_bwd_run(b, w, walk_recs(b, w),
+               [&] {
+                   hipLaunchKernelGGL(partial, grid, dim3(BN_THREADS), 0, b.s, view_ptr<const T>(y), y.ldc, P, w,
+                                      b.rec);
+               },
+               [&](float *brec) {
+                   hipLaunchKernelGGL(apply, grid, dim3(BN_THREADS), 0, b.s, view_ptr<const T>(y), y.ldc, P,
+                                      view_ptr<T>(b.dy), b.dy.ldc, w, brec, b.dy_bound);
+               });
 }
 }  // namespace scd
 
@@ -1527,23 +1435,12 @@ extern "C" int scd_bn_relu_backward(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, c
                                     const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
                                     scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
     clear_error();
-    SCD_TRY(bn_check(y, nseg));
-    SCD_TRY(check_view(da, "bn_bwd.da"));
-    SCD_TRY(check_view(dy, "bn_bwd.dy"));
-    if (da.n != y.n || da.h != y.h || da.w != y.w || da.c != y.c || dy.n != y.n || dy.h != y.h || dy.w != y.w ||
-        dy.c != y.c || !save_mean || !save_invstd || !scale || !shift) {
-        set_error("bn_relu_backward: shape mismatch / null");
-        return SCD_ERR_ARG;
-    }
-    if (!ws || ws_bytes < scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, nseg)) {
-        set_error("bn_relu_backward: workspace too small");
-        return SCD_ERR_WORKSPACE;
-    }
+    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
+            as_stream(stream)};
+    SCD_TRY(bn_bwd_check("bn_relu_backward", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}}));
     const int dt = common_dtype("bn_relu_backward", {&y, &da, &dy});
     if (dt < 0) return SCD_ERR_ARG;
-    SCD_WITH_T(dt, T,
-               bn_backward_run<T>(y, DaPlain<T>{view_ptr<const T>(da), da.ldc}, nseg, save_mean, save_invstd, gamma,
-                                  scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, as_stream(stream)));
+    SCD_WITH_T(dt, T, bn_backward_run<T>(b, DaPlain<T>{view_ptr<const T>(da), da.ldc}));
     return launch_status("scd_bn_relu_backward");
 }
 
@@ -1561,32 +1458,23 @@ extern "C" int scd_bn_relu_backward_head(scd_nhwc_t y, const float *gout, const 
                                          float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
                                          float *w_grad, void *ws, size_t ws_bytes, scd_stream_t stream) {
     clear_error();
-    SCD_TRY(bn_check(y, nseg));
-    SCD_TRY(check_view(dy, "bn_bwd_head.dy"));
-    if (!gout || !w_head || n_out < 1 || n_out > 4 || dy.n != y.n || dy.h != y.h || dy.w != y.w || dy.c != y.c ||
-        !save_mean || !save_invstd || !scale || !shift || pixels(y) >= (int64_t(1) << 31)) {
-        set_error("bn_relu_backward_head: shape mismatch / null / n_out not in [1,4] / 2^31 pixels or more");
+    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
+            as_stream(stream)};
+    const size_t need = w_grad ? scd_bn_head_workspace_bytes(y.n, y.h, y.w, y.c, nseg, n_out) : 0;
+    SCD_TRY(bn_bwd_check("bn_relu_backward_head", b, {{&dy, "bn_bwd_head.dy", false, true}}, need, [&] {
+        if (gout && w_head && n_out >= 1 && n_out <= 4 && pixels(y) < (int64_t(1) << 31)) return SCD_OK;
+        set_error("bn_relu_backward_head: null gradient or weights / n_out not in [1,4] / 2^31 pixels or more");
         return SCD_ERR_ARG;
-    }
-    const size_t need = w_grad ? scd_bn_head_workspace_bytes(y.n, y.h, y.w, y.c, nseg, n_out)
-                               : scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, nseg);
-    if (!ws || ws_bytes < need) {
-        set_error("bn_relu_backward_head: workspace %zu < %zu bytes", ws_bytes, need);
-        return SCD_ERR_WORKSPACE;
-    }
+    }));
     const DaHead da{gout, w_head, n_out, y.c, y.h * y.w, make_fastdiv(uint32_t(y.h * y.w))};
     const int dt = common_dtype("bn_relu_backward_head", {&y, &dy});
     if (dt < 0) return SCD_ERR_ARG;
     auto run = [&](auto no) {
         constexpr int NO = decltype(no)::value;
         if (w_grad) {
-            SCD_WITH_T(dt, T,
-                       (bn_backward_run_head<T, NO>(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma,
-                                                    dbeta, dbias_prev, dy, dy_bound, w_grad, ws, as_stream(stream))));
+            SCD_WITH_T(dt, T, (bn_backward_run_head<T, NO>(b, da, w_grad)));
         } else {
-            SCD_WITH_T(dt, T,
-                       bn_backward_run<T>(y, DaHeadN<NO>{da, {}}, nseg, save_mean, save_invstd, gamma, scale, shift,
-                                          dgamma, dbeta, dbias_prev, dy, dy_bound, ws, as_stream(stream)));
+            SCD_WITH_T(dt, T, bn_backward_run<T>(b, DaHeadN<NO>{da, {}}));
         }
     };
     switch (n_out) {
@@ -1619,60 +1507,62 @@ extern "C" int scd_bn_relu_backward_pooled2(scd_nhwc_t y, scd_nhwc_t gy, const u
                                             float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
                                             size_t ws_bytes, scd_stream_t stream) {
     clear_error();
-    SCD_TRY(bn_check(y, nseg));
-    SCD_TRY(check_view(gy, "bn_bwd_pooled.gy", true));
-    SCD_TRY(check_view(gskip, "bn_bwd_pooled.gskip", true));
-    SCD_TRY(check_view(gskip2, "bn_bwd_pooled.gskip2", true));
-    SCD_TRY(check_view(dy, "bn_bwd_pooled.dy"));
-    if (dy.n != y.n || dy.h != y.h || dy.w != y.w || dy.c != y.c || !save_mean || !save_invstd || !scale || !shift ||
-        (!gy.data && !gskip.data) || pixels(y) >= (int64_t(1) << 31)) {
-        set_error("bn_relu_backward_pooled: shape mismatch / null");
-        return SCD_ERR_ARG;
-    }
-    if (gy.data && (!idx || gy.n != y.n || gy.c != y.c || gy.h != y.h / 2 || gy.w != y.w / 2 ||
-                    (reinterpret_cast<uintptr_t>(idx) & 3))) {
-        set_error("bn_relu_backward_pooled: gy must be (n, h/2, w/2, c) with 4-byte aligned idx");
-        return SCD_ERR_ARG;
-    }
-    if (gskip.data && (gskip.c != y.c || gskip.h != y.h || gskip.w != y.w || y.n % gskip.n ||
-                       (skip_mode != 0 && y.n != 2 * gskip.n) || skip_mode < 0 || skip_mode > 2)) {
-        set_error("bn_relu_backward_pooled: gskip shape/mode mismatch");
-        return SCD_ERR_ARG;
-    }
-    if ((skip_mode == 2) != (gskip2.data != nullptr) ||
-        (gskip2.data && (!gskip.data || nseg != 2 || gskip2.n != y.n || gskip2.h != y.h || gskip2.w != y.w ||
-                         gskip2.c != y.c))) {
-        set_error("bn_relu_backward_pooled: skip_mode 2 needs gskip (n/2 images), gskip2 (n images) and nseg 2; "
-                  "gskip2 only with skip_mode 2");
-        return SCD_ERR_ARG;
-    }
-    if (!ws || ws_bytes < scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, nseg)) {
-        set_error("bn_relu_backward_pooled: workspace too small");
-        return SCD_ERR_WORKSPACE;
-    }
+    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
+            as_stream(stream)};
+    const auto more = [&] {
+        if ((!gy.data && !gskip.data) || pixels(y) >= (int64_t(1) << 31)) {
+            set_error("bn_relu_backward_pooled: neither gy nor gskip / 2^31 pixels or more");
+            return SCD_ERR_ARG;
+        }
+        if (gy.data && (!idx || gy.n != y.n || gy.c != y.c || gy.h != y.h / 2 || gy.w != y.w / 2 ||
+                        (reinterpret_cast<uintptr_t>(idx) & 3))) {
+            set_error("bn_relu_backward_pooled: gy must be (n, h/2, w/2, c) with 4-byte aligned idx");
+            return SCD_ERR_ARG;
+        }
+        if (gskip.data && (gskip.c != y.c || gskip.h != y.h || gskip.w != y.w || y.n % gskip.n ||
+                           (skip_mode != 0 && y.n != 2 * gskip.n) || skip_mode < 0 || skip_mode > 2)) {
+            set_error("bn_relu_backward_pooled: gskip shape/mode mismatch");
+            return SCD_ERR_ARG;
+        }
+        if ((skip_mode == 2) != (gskip2.data != nullptr) ||
+            (gskip2.data && (!gskip.data || nseg != 2 || gskip2.n != y.n || gskip2.h != y.h || gskip2.w != y.w ||
+                             gskip2.c != y.c))) {
+            set_error("bn_relu_backward_pooled: skip_mode 2 needs gskip (n/2 images), gskip2 (n images) and nseg 2; "
+                      "gskip2 only with skip_mode 2");
+            return SCD_ERR_ARG;
+        }
+        return SCD_OK;
+    };
+    SCD_TRY(bn_bwd_check("bn_relu_backward_pooled", b,
+                         {{&gy, "bn_bwd_pooled.gy", true, false},
+                          {&gskip, "bn_bwd_pooled.gskip", true, false},
+                          {&gskip2, "bn_bwd_pooled.gskip2", true, false},
+                          {&dy, "bn_bwd_pooled.dy", false, true}},
+                         0, more));
     const int dt = common_dtype("bn_relu_backward_pooled", {&y, &gy, &gskip, &gskip2, &dy});
     if (dt < 0) return SCD_ERR_ARG;
     SCD_WITH_T(dt, T, {
-        DaPooled<T> da;
-        da.gy = view_ptr<const T>(gy);
-        da.idx = idx;
-        da.hy = gy.h;
-        da.wy = gy.w;
-        da.ldgy = gy.ldc;
-        da.gs = view_ptr<const T>(gskip);
-        da.gsn = gskip.n > 0 ? gskip.n : 1;
-        da.ldgs = gskip.ldc;
-        da.skip_mode = skip_mode;
-        da.gs2 = view_ptr<const T>(gskip2);
-        da.ldgs2 = gskip2.ldc;
-        da.hx = y.h;
-        da.wx = y.w;
-        da.C = y.c;
-        da.div_hw = make_fastdiv(uint32_t(y.h * y.w));
-        da.div_w = make_fastdiv(uint32_t(y.w));
-        da.div_gsn = make_fastdiv(uint32_t(da.gsn));
-        bn_backward_run_pooled<T>(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev,
-                                  dy, dy_bound, ws, as_stream(stream));
+        PooledCells<T> P{};
+        P.gy = view_ptr<const T>(gy);
+        P.idx = idx;
+        P.hy = gy.h;
+        P.wy = gy.w;
+        P.ldgy = gy.ldc;
+        P.gs = view_ptr<const T>(gskip);
+        P.gsn = gskip.n > 0 ? gskip.n : 1;
+        P.ldgs = gskip.ldc;
+        P.skip_mode = skip_mode;
+        P.gs2 = view_ptr<const T>(gskip2);
+        P.ldgs2 = gskip2.ldc;
+        P.hx = y.h;
+        P.wx = y.w;
+        P.C = y.c;
+        P.div_gsn = make_fastdiv(uint32_t(P.gsn));
+        if (P.gs2) {
+            bn_backward_run_pooled<T, true>(b, P);
+        } else {
+            bn_backward_run_pooled<T, false>(b, P);
+        }
     });
     return launch_status("scd_bn_relu_backward_pooled");
 }
@@ -1683,34 +1573,22 @@ extern "C" int scd_bn_relu_backward_tiles(scd_nhwc_t y, scd_nhwc_t da, int32_t n
                                           float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes,
                                           scd_stream_t stream) {
     clear_error();
-    SCD_TRY(bn_check(y, nseg));
-    SCD_TRY(check_view(da, "bn_bwd.da"));
-    SCD_TRY(check_view(dy, "bn_bwd.dy"));
-    if (da.n != y.n || da.h != y.h || da.w != y.w || da.c != y.c || dy.n != y.n || dy.h != y.h || dy.w != y.w ||
-        dy.c != y.c || !save_mean || !save_invstd || !scale || !shift || !tile_rec || ntiles < nseg ||
-        ntiles % nseg || pixels(y) % ntiles) {
-        set_error("bn_relu_backward_tiles: shape mismatch / null / %d tiles not divisible into %d segments", ntiles,
-                  nseg);
-        return SCD_ERR_ARG;
-    }
-    if (!ws || ws_bytes < scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, nseg)) {
-        set_error("bn_relu_backward_tiles: workspace too small");
-        return SCD_ERR_WORKSPACE;
-    }
-    const BnGeom g = bn_geom(y, nseg);
-    float *brec = static_cast<float *>(ws);
-    float *coef = brec + size_t(g.nrec) * y.c;
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(bn_bwd_finalize, dim3(y.c), dim3(BN_THREADS), 0, s, tile_rec, y.c, nseg, ntiles / nseg, ntiles,
-                       g.pseg, coef, dgamma, dbeta);
+    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
+            as_stream(stream)};
+    SCD_TRY(bn_bwd_check("bn_relu_backward_tiles", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}},
+                         0, [&] {
+                             if (tile_rec && ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)
+                                 return SCD_OK;
+                             set_error("bn_relu_backward_tiles: null records / %d tiles not divisible into %d "
+                                       "segments", ntiles, nseg);
+                             return SCD_ERR_ARG;
+                         }));
     const int dt = common_dtype("bn_relu_backward_tiles", {&y, &da, &dy});
     if (dt < 0) return SCD_ERR_ARG;
+    const BnWalk w = b.pixel_walk();
     SCD_WITH_T(dt, T,
-               hipLaunchKernelGGL((bn_bwd_apply<T, DaPlain<T>>), dim3(g.nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                                  view_ptr<const T>(y), y.ldc, DaPlain<T>{view_ptr<const T>(da), da.ldc},
-                                  view_ptr<T>(dy), dy.ldc, y.c, g.pseg, g.ncps, g.chunk, g.nrec, g.qpb, save_mean,
-                                  save_invstd, gamma, scale, shift, coef, dbias_prev ? brec : nullptr, dy_bound));
-    if (dbias_prev) hipLaunchKernelGGL(sum_records, dim3(y.c), dim3(BN_THREADS), 0, s, brec, g.nrec, dbias_prev);
+               bn_bwd_run(b, w, tile_recs(b, tile_rec, ntiles), NoStep{},
+                          pixel_apply<T>(b, w, DaPlain<T>{view_ptr<const T>(da), da.ldc})));
     return launch_status("scd_bn_relu_backward_tiles");
 }
 
@@ -1720,36 +1598,26 @@ extern "C" int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t ns
                                          float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
                                          float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
     clear_error();
-    SCD_TRY(bn_check(y, nseg));
-    SCD_TRY(check_view(da, "bn_bwd_coef.da", tile_rec != nullptr));
-    if ((!tile_rec && (da.n != y.n || da.h != y.h || da.w != y.w || da.c != y.c)) || !save_mean || !save_invstd ||
-        !scale || !shift || !coef || (tile_rec && (ntiles < nseg || ntiles % nseg || pixels(y) % ntiles)) ||
-        (dy_bound && !da_bound)) {
-        set_error("bn_relu_backward_coef: shape mismatch / null / %d tiles not divisible into %d segments / dy_bound "
-                  "without da_bound", ntiles, nseg);
+    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, scd_nhwc_t{}, dy_bound, ws,
+            ws_bytes, as_stream(stream)};
+    SCD_TRY(bn_bwd_check("bn_relu_backward_coef", b, {{&da, "bn_bwd_coef.da", tile_rec != nullptr, !tile_rec}}, 0, [&] {
+        if (coef && (!tile_rec || (ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)) &&
+            (!dy_bound || da_bound))
+            return SCD_OK;
+        set_error("bn_relu_backward_coef: null coef / %d tiles not divisible into %d segments / dy_bound without "
+                  "da_bound", ntiles, nseg);
         return SCD_ERR_ARG;
-    }
-    if (!ws || ws_bytes < scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, nseg)) {
-        set_error("bn_relu_backward_coef: workspace too small");
-        return SCD_ERR_WORKSPACE;
-    }
-    const BnGeom g = bn_geom(y, nseg);
-    hipStream_t s = as_stream(stream);
+    }));
+    b.coef = coef;  // the caller's, not the workspace's
+    const BnWalk w = b.pixel_walk();
     if (tile_rec) {
-        hipLaunchKernelGGL(bn_bwd_finalize, dim3(y.c), dim3(BN_THREADS), 0, s, tile_rec, y.c, nseg, ntiles / nseg,
-                           ntiles, g.pseg, coef, dgamma, dbeta, gamma, save_invstd, dbias_prev, save_mean, da_bound,
-                           dy_bound);
+        bn_bwd_run(b, w, tile_recs(b, tile_rec, ntiles), NoStep{}, NoStep{}, da_bound);
     } else {
-        float *rec = static_cast<float *>(ws);
         const int dt = common_dtype("bn_relu_backward_coef", {&y, &da});
         if (dt < 0) return SCD_ERR_ARG;
         SCD_WITH_T(dt, T,
-                   hipLaunchKernelGGL((bn_bwd_partial<T, DaPlain<T>>), dim3(g.nrec, g.cgroups), dim3(BN_THREADS), 0, s,
-                                      view_ptr<const T>(y), y.ldc, DaPlain<T>{view_ptr<const T>(da), da.ldc}, y.c,
-                                      g.pseg, g.ncps, g.chunk, g.nrec, g.qpb, save_mean, save_invstd, scale, shift,
-                                      rec));
-        hipLaunchKernelGGL(bn_bwd_finalize, dim3(y.c), dim3(BN_THREADS), 0, s, rec, y.c, nseg, g.ncps, g.nrec, g.pseg,
-                           coef, dgamma, dbeta, gamma, save_invstd, dbias_prev, save_mean, da_bound, dy_bound);
+                   bn_bwd_run(b, w, walk_recs(b, w), pixel_partial<T>(b, w, DaPlain<T>{view_ptr<const T>(da), da.ldc}),
+                              NoStep{}, da_bound));
     }
     return launch_status("scd_bn_relu_backward_coef");
 }

@@ -75,6 +75,13 @@ inline int launch_status(const char *what) {
     return SCD_OK;
 }
 
+// bn_f32.hip, also the 1x1 head's weight grad (misc_f32.hip): out[c] = sum_p w(p) v[p][c] over all pixels, w = 1 or
+// gout[img][o][pix], v = x or (scale / shift given, per segment of nseg) relu(fma(x, scale, shift)).
+int weighted_channel_sum(const scd_nhwc_t &x, const float *wgt, int n_out, int o, float *out, void *ws,
+                         size_t ws_bytes, hipStream_t s, const float *scale = nullptr, const float *shift = nullptr,
+                         int nseg = 1);
+size_t weighted_channel_sum_bytes(const scd_nhwc_t &x);
+
 #define SCD_TRY(expr)                 \
     do {                              \
         int _rc = (expr);             \

@@ -24,12 +24,6 @@ void set_error(const char *fmt, ...) {
 }
 void clear_error() { g_err.clear(); }
 
-// bn_f32.hip: sum_p w(p) x[p][c] over all pixels (w = 1 or gout[img][o][pix]).
-int weighted_channel_sum(const scd_nhwc_t &x, const float *wgt, int n_out, int o, float *out, void *ws,
-                         size_t ws_bytes, hipStream_t s, const float *scale = nullptr, const float *shift = nullptr,
-                         int nseg = 1);
-size_t weighted_channel_sum_bytes(const scd_nhwc_t &x);
-
 // Row-decomposed grid: x covers the quads of one row (256 per block), y walks rows (grid-stride past 65535).
 static dim3 row_grid(int row_quads, int64_t rows) {
     return dim3(unsigned((row_quads + 255) / 256), unsigned(rows < 65535 ? rows : 65535));

@@ -854,7 +854,7 @@ def test_bn_relu_fused_pool_and_diff(dev, n, h, w, c, nseg):
 def test_bn_relu_backward_pooled(dev, n, h, w, c, mode, parts):
     """The BatchNorm + ReLU backward forming its incoming gradient on the fly (maxpool_bwd -/+ skip) over 2x2 cells:
     feature_grad followed by bn_relu_backward (dy, dgamma, dbeta, conv-bias grad) up to the order of the per-chunk
-    sums (2e-6).  (The per-pixel walk, -DSCD_BN_POOLED_CELLS=0, is bit-identical to the unfused pair.)"""
+    sums (2e-6): the cell walk chunks each segment by cells, the unfused pair by pixels."""
     from multimodal_siamese_cd_amd import hip
     g = torch.Generator().manual_seed(n * h * w + c + mode)
     nseg = 2
