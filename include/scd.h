@@ -155,8 +155,9 @@ enum scd_conv_math {
  *   9: scd_igemm_t.dst_bound_seed appended (a bound seeded with another buffer's bound inside the conv launch).
  *      Still 9 (no layout or signature change): three tune selectors were withdrawn with their kernels, all measured
  *      slower -- the late halo load (bit 27), the warp-specialized h2 tiles (bit 29) and the double-buffered h2
- *      weight grad (bit 31). */
-#define SCD_ABI_VERSION 9
+ *      weight grad (bit 31).
+ *  10: the loss family appended (scd_loss_kind_t, scd_loss_term_t, scd_loss_multi_*); nothing existing changes. */
+#define SCD_ABI_VERSION 10
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
  * the shape or the missing operand bounds keep the conv off the requested kernels); negative = invalid descriptor.
@@ -611,6 +612,58 @@ int scd_pjaccard_loss_from_sums(float *sums, float *loss, scd_stream_t stream);
  * train_semisupervised.py:107, where the target sigma(logits_s2) is not detached). */
 int scd_pjaccard_bwd(const float *logits, const float *target, int64_t n, const float *sums,
                      const float *gloss, float *glogits, float *gtarget, scd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The loss family: the other criteria utils/loss_functions.py:6-33 registers and the MMCR `L2` consistency branch
+ * (train_semisupervised.py:101-102), fused multi-term like scd_jaccard_multi_* and with its term semantics (subsets
+ * selected on the device, an empty subset contributes nothing, a soft target = sigmoid(target logits) is not
+ * detached and receives a gradient, zero_unselected as above).  p = sigmoid(logit), t = target, sums over the
+ * selected elements, N = their number, e = 1e-6, I = sum p t, P = sum p, T = sum t, Q = sum (p^2 + t^2):
+ *   SCD_LOSS_POWER_JACCARD       1 - I / (Q - I + e)                                   loss_functions.py:141-150
+ *   SCD_LOSS_SOFT_DICE           1 - (2I + e) / (P + T + e)                            :36-56
+ *   SCD_LOSS_SOFT_DICE_BALANCED  1 - 2I / (P + T + e) - 2(N - P - T + I) / (2N - P - T + e)   :184-198
+ *   SCD_LOSS_IOU                 1 - I / (P + T - I + e)                               :153-162
+ *   SCD_LOSS_DICE_LIKE           1 - 2I / (Q + e)                                      :129-138
+ *   SCD_LOSS_BCE_LOGITS          mean(max(x, 0) - x t + log1p(exp(-|x|)))              nn.BCEWithLogitsLoss
+ *   SCD_LOSS_MSE                 mean((u - t)^2), u = the raw logit (nn.MSELoss on logits, sigmoid_input 0) or
+ *                                sigmoid(logit) (sigmoid_input 1: the L2 consistency loss with a soft target)
+ *   loss = sum_t coef_t * [|sel_t| > 0] * loss_t
+ * sums (device float[n_terms][8]) = {I (pointwise kinds: the sum of the per-element expression), P, T, Q, |sel| in
+ * samples, a, b, c}; sums a kind does not need are 0.  a, b, c are the backward's coefficients (ratio kinds:
+ * dloss_t/dp_i = a + b t_i + c p_i, and the same with p and t swapped for a soft target; pointwise kinds: a = 1/N).
+ * `labeled` may be NULL when every term selects all samples.
+ * Exact-DataParallel form: all-reduce `sums` (SUM) after the fwd call, then scd_loss_multi_loss_from_sums re-forms
+ * the coefficients and the loss from the global rows in place (N = global sample count * pixels); the bwd call then
+ * takes the global rows. */
+typedef enum scd_loss_kind {
+    SCD_LOSS_POWER_JACCARD = 0,
+    SCD_LOSS_SOFT_DICE = 1,
+    SCD_LOSS_SOFT_DICE_BALANCED = 2,
+    SCD_LOSS_IOU = 3,
+    SCD_LOSS_DICE_LIKE = 4,
+    SCD_LOSS_BCE_LOGITS = 5,
+    SCD_LOSS_MSE = 6,
+    SCD_LOSS_KIND_COUNT = 7
+} scd_loss_kind_t;
+typedef struct scd_loss_term {
+    const float *logits;
+    const float *target;
+    float *glogits;
+    float *gtarget;
+    float coef;
+    int32_t kind;            /* scd_loss_kind_t */
+    int32_t select;          /* 0: all samples, 1: labeled[s] != 0, 2: labeled[s] == 0 */
+    int32_t soft_target;
+    int32_t sigmoid_input;   /* SCD_LOSS_MSE only: 0 = raw logits, 1 = sigmoid(logits) */
+    int32_t zero_unselected; /* bit 0: glogits, bit 1: gtarget */
+} scd_loss_term_t;
+size_t scd_loss_multi_workspace_bytes(int32_t n_terms);
+int scd_loss_multi_fwd(const scd_loss_term_t *terms, int32_t n_terms, const uint8_t *labeled, int32_t n_samples,
+                       int64_t pixels, float *sums, float *loss, void *ws, size_t ws_bytes, scd_stream_t stream);
+int scd_loss_multi_loss_from_sums(const scd_loss_term_t *terms, int32_t n_terms, int64_t pixels, float *sums,
+                                  float *loss, scd_stream_t stream);
+int scd_loss_multi_bwd(const scd_loss_term_t *terms, int32_t n_terms, const uint8_t *labeled, int32_t n_samples,
+                       int64_t pixels, const float *sums, const float *gloss, scd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Eval path

@@ -11,6 +11,7 @@ calls on NHWC fp32 device buffers, and its backward as the reverse sequence:
   HeadFn                   OutConv 1x1                                     networks.py:454-461
   CatFn                    torch.cat(..., dim=1) of decoder outputs        networks.py:119, 258
   PJaccardFn               power_jaccard_loss                              loss_functions.py:141-150
+  MultiLossFn              the other registered criteria, fused terms      loss_functions.py:6-33, 36-198
 
 The Siamese encoder runs both branches as ONE 2B-image batch (weights shared) with BatchNorm
 statistics segmented per branch (nseg = 2), which reproduces the reference's two separate module calls
@@ -1684,3 +1685,87 @@ class MultiJaccardFn(torch.autograd.Function):
 def multi_jaccard(spec, labeled: torch.Tensor, *tensors) -> torch.Tensor:
     hip.ensure_device(tensors[0])
     return MultiJaccardFn.apply(spec, labeled, *tensors)
+
+
+# ------------------------------------------------------------------------------------------------
+# The loss family (every other criterion of utils/loss_functions.get_criterion, and the MMCR L2 consistency term)
+# ------------------------------------------------------------------------------------------------
+def _loss_spec(spec):
+    """Spec entries (logits index, target index, coef, select, soft[, kind[, sigmoid_input]]) in full."""
+    return [tuple(e) + (hip.LOSS_POWER_JACCARD, 0)[len(e) - 5:] for e in spec]
+
+
+class MultiLossFn(torch.autograd.Function):
+    """sum_t coef_t * [|sel_t| > 0] * loss_kind_t(logits_t[sel_t], target_t[sel_t]) in one fused pass
+    (scd_loss_multi_fwd/bwd).  spec: per term (logits index, target index, coef, select, soft, kind, sigmoid_input)
+    into `tensors`; select and soft as MultiJaccardFn, kind a hip.LOSS_* value, sigmoid_input (LOSS_MSE only) takes
+    sigmoid(logits) instead of the raw logits.  No host sync: empty subsets are dropped on the device."""
+
+    @staticmethod
+    def forward(ctx, spec, labeled, *tensors):
+        spec = _loss_spec(spec)
+        ts = [t.contiguous().float() for t in tensors]
+        n_samples = ts[0].shape[0]
+        pixels = ts[0].numel() // n_samples
+        for t in ts:
+            if t.numel() != n_samples * pixels:
+                raise ValueError(f"multi-term loss: tensor of {t.numel()} elements, expected {n_samples * pixels}")
+        if labeled is None:
+            if any(e[3] != 0 for e in spec):
+                raise ValueError("multi-term loss: a term selects a subset but there is no labelled mask")
+            lab = None
+        else:
+            lab = labeled.to(device=ts[0].device, dtype=torch.uint8).contiguous()
+        terms = [dict(logits=ts[li], target=ts[ti], coef=c, select=sel, soft=soft, kind=kind, sigmoid_input=sig)
+                 for li, ti, c, sel, soft, kind, sig in spec]
+        sums = _empty((len(spec), hip.LOSS_ROW), ts[0])
+        loss = _empty((), ts[0])
+        hip.loss_multi_fwd(terms, lab, n_samples, pixels, sums, loss)
+        red = _LOSS_ALLREDUCE.get()
+        if red is not None:  # exact-DataParallel: every term over the samples of all ranks
+            red(sums)
+            hip.loss_multi_loss_from_sums(terms, pixels, sums, loss)
+        ctx.spec, ctx.dims, ctx.lab = spec, (n_samples, pixels), lab
+        ctx.save_for_backward(sums, *ts)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        sums, *ts = ctx.saved_tensors
+        n_samples, pixels = ctx.dims
+        need = ctx.needs_input_grad[2:]
+        grads = [torch.empty_like(t) if need[i] else None for i, t in enumerate(ts)]
+        # the writer / overlap rule of MultiJaccardFn.backward
+        writers = [[] for _ in ts]
+        for k, (li, ti, _, sel, soft, _, _) in enumerate(ctx.spec):
+            writers[li].append((k, 1, sel))
+            if soft:
+                writers[ti].append((k, 2, sel))
+        zero = [0] * len(ctx.spec)
+        for i, w in enumerate(writers):
+            sels = [sel for _, _, sel in w]
+            if len(sels) > 1 and (0 in sels or len(set(sels)) != len(sels)):
+                raise NotImplementedError("multi-term loss: a tensor in two terms over overlapping samples")
+            if grads[i] is not None and len(w) == 1 and sels[0] != 0:
+                zero[w[0][0]] |= w[0][1]
+        terms = [dict(logits=ts[li], target=ts[ti], coef=c, select=sel, soft=soft, kind=kind, sigmoid_input=sig,
+                      glogits=grads[li], gtarget=grads[ti] if soft else None, zero=zero[k])
+                 for k, (li, ti, c, sel, soft, kind, sig) in enumerate(ctx.spec)]
+        hip.loss_multi_bwd(terms, ctx.lab, n_samples, pixels, sums, g.contiguous())
+        return (None, None, *grads)
+
+
+def multi_loss(spec, labeled, *tensors) -> torch.Tensor:
+    hip.ensure_device(tensors[0])
+    return MultiLossFn.apply(spec, labeled, *tensors)
+
+
+def single_loss(kind: int, logits: torch.Tensor, target: torch.Tensor, soft: bool = False,
+                sigmoid_input: bool = False) -> torch.Tensor:
+    """One criterion of the family over the whole batch (the plain `criterion(logits, y)` call).  soft: `target` holds
+    the logits of a sigmoid target, which receives a gradient."""
+    if logits.numel() != target.numel():
+        raise ValueError(f"loss: {logits.numel()} logits vs {target.numel()} targets")
+    if not soft and target.requires_grad:
+        raise NotImplementedError("loss: a target that needs a gradient must be given as its logits (soft=True)")
+    return multi_loss([(0, 1, 1.0, 0, int(soft), kind, int(sigmoid_input))], None, logits, target)

@@ -203,13 +203,18 @@ _SIGS = {
     "scd_jaccard_multi_fwd": ([c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p], c_int),
     "scd_jaccard_multi_bwd": ([c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p], c_int),
+    "scd_loss_multi_workspace_bytes": ([c_int32], c_size_t),
+    "scd_loss_multi_fwd": ([c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                            c_void_p], c_int),
+    "scd_loss_multi_loss_from_sums": ([c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p], c_int),
+    "scd_loss_multi_bwd": ([c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p], c_int),
     "scd_threshold_counts_workspace_bytes": ([c_int64, c_int32], c_size_t),
     "scd_threshold_counts": (
         [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
-ABI_VERSION = 9  # SCD_ABI_VERSION of include/scd.h
+ABI_VERSION = 10  # SCD_ABI_VERSION of include/scd.h
 
 
 def load_library(path: str = LIB_PATH):
@@ -1022,3 +1027,47 @@ def jaccard_multi_loss_from_sums(terms, sums, loss):
     arr = _jterms(terms)
     _check(lib().scd_jaccard_multi_loss_from_sums(ctypes.cast(arr, c_void_p), len(terms), sums.data_ptr(),
                                                   loss.data_ptr(), _stream()), "scd_jaccard_multi_loss_from_sums")
+
+
+# scd_loss_kind_t
+LOSS_POWER_JACCARD, LOSS_SOFT_DICE, LOSS_SOFT_DICE_BALANCED, LOSS_IOU, LOSS_DICE_LIKE, LOSS_BCE_LOGITS, LOSS_MSE = range(7)
+LOSS_ROW = 8  # floats per sums row: {I | E, P, T, Q, selected samples, a, b, c}
+
+
+class LTERM(ctypes.Structure):
+    _fields_ = [("logits", c_void_p), ("target", c_void_p), ("glogits", c_void_p), ("gtarget", c_void_p),
+                ("coef", c_float), ("kind", c_int32), ("select", c_int32), ("soft_target", c_int32),
+                ("sigmoid_input", c_int32), ("zero_unselected", c_int32)]
+
+
+def _lterms(terms):
+    arr = (LTERM * len(terms))()
+    for i, t in enumerate(terms):
+        arr[i] = LTERM(_ptr(t['logits']), _ptr(t['target']), _ptr(t.get('glogits')), _ptr(t.get('gtarget')),
+                       float(t['coef']), int(t['kind']), int(t['select']), int(t.get('soft', 0)),
+                       int(t.get('sigmoid_input', 0)), int(t.get('zero', 0)))
+    return arr
+
+
+def loss_multi_fwd(terms, labeled, n_samples: int, pixels: int, sums, loss):
+    """terms: dicts {logits, target, coef, kind, select, soft, sigmoid_input}; labeled: device uint8 [n_samples], or
+    None when every term selects all samples; sums: device float [n_terms][LOSS_ROW]."""
+    ws = torch.empty(lib().scd_loss_multi_workspace_bytes(len(terms)), dtype=torch.uint8, device=sums.device)
+    arr = _lterms(terms)
+    _check(lib().scd_loss_multi_fwd(ctypes.cast(arr, c_void_p), len(terms), _ptr(labeled), n_samples, pixels,
+                                    sums.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+           "scd_loss_multi_fwd")
+
+
+def loss_multi_bwd(terms, labeled, n_samples: int, pixels: int, sums, gloss):
+    """terms as loss_multi_fwd plus {glogits, gtarget, zero}."""
+    arr = _lterms(terms)
+    _check(lib().scd_loss_multi_bwd(ctypes.cast(arr, c_void_p), len(terms), _ptr(labeled), n_samples, pixels,
+                                    sums.data_ptr(), _ptr(gloss), _stream()), "scd_loss_multi_bwd")
+
+
+def loss_multi_loss_from_sums(terms, pixels: int, sums, loss):
+    """Coefficients and loss re-formed from (all-reduced) rows [n_terms][LOSS_ROW] in place (exact-DataParallel)."""
+    arr = _lterms(terms)
+    _check(lib().scd_loss_multi_loss_from_sums(ctypes.cast(arr, c_void_p), len(terms), pixels, sums.data_ptr(),
+                                               loss.data_ptr(), _stream()), "scd_loss_multi_loss_from_sums")

@@ -3,8 +3,13 @@
   supervised  train_supervised.py:63-79            loss = criterion(logits, y_change)
   dual task   train_supervised_dualtask.py:64-90   (L_change + (L_sem_t1 + L_sem_t2) / 2) / 2
   MMCR        train_semisupervised.py:66-121       alpha * mean(L_fusion, L_s1, L_s2) on labelled samples
-                                                   + (1 - alpha) * PJ(logits_s1, sigmoid(logits_s2)) on unlabelled
-                                                   (the soft target is NOT detached, as in the reference)
+                                                   + (1 - alpha) * L_cons(logits_s1, sigmoid(logits_s2)) on unlabelled
+                                                   (the soft target is NOT detached, as in the reference; LOSS_TYPE
+                                                   L2: MSE(sigmoid(logits_s1), sigmoid(logits_s2)), lines 101-102)
+
+Criteria of utils/loss_functions.py carry the kind of their fused kernel, so every recipe is one fused multi-term call
+(engine.multi_jaccard when every term is PowerJaccardLoss, engine.multi_loss otherwise); a foreign callable takes the
+reference's boolean-mask composition.
 """
 from __future__ import annotations
 
@@ -15,6 +20,11 @@ from .utils import loss_functions
 
 
 def _fusable(*criteria) -> bool:
+    """Every criterion is one of ours (utils/loss_functions.py): it carries the kind of its fused kernel."""
+    return all(isinstance(getattr(c, 'kind', None), int) for c in criteria)
+
+
+def _all_power_jaccard(*criteria) -> bool:
     return all(c is loss_functions.power_jaccard_loss for c in criteria)
 
 
@@ -25,10 +35,15 @@ def supervised_loss(criterion, logits, batch):
 def dualtask_loss(change_criterion, sem_criterion, outputs, batch):
     logits_change, logits_sem_t1, logits_sem_t2 = outputs
     if _fusable(change_criterion, sem_criterion):  # one fused pass: 0.5 L_change + 0.25 L_sem_t1 + 0.25 L_sem_t2
-        lab = torch.ones(logits_change.shape[0], dtype=torch.uint8, device=logits_change.device)
-        spec = [(0, 1, 0.5, 0, 0), (2, 3, 0.25, 0, 0), (4, 5, 0.25, 0, 0)]
-        return engine.multi_jaccard(spec, lab, logits_change, batch['y_change'], logits_sem_t1, batch['y_sem_t1'],
-                                    logits_sem_t2, batch['y_sem_t2'])
+        tensors = (logits_change, batch['y_change'], logits_sem_t1, batch['y_sem_t1'], logits_sem_t2,
+                   batch['y_sem_t2'])
+        if _all_power_jaccard(change_criterion, sem_criterion):  # the shipped configs: the dedicated kernels
+            lab = torch.ones(logits_change.shape[0], dtype=torch.uint8, device=logits_change.device)
+            spec = [(0, 1, 0.5, 0, 0), (2, 3, 0.25, 0, 0), (4, 5, 0.25, 0, 0)]
+            return engine.multi_jaccard(spec, lab, *tensors)
+        kc, ks = change_criterion.kind, sem_criterion.kind
+        spec = [(0, 1, 0.5, 0, 0, kc, 0), (2, 3, 0.25, 0, 0, ks, 0), (4, 5, 0.25, 0, 0, ks, 0)]
+        return engine.multi_loss(spec, None, *tensors)
     change_loss = change_criterion(logits_change, batch['y_change'])
     sem_loss = (sem_criterion(logits_sem_t1, batch['y_sem_t1']) + sem_criterion(logits_sem_t2, batch['y_sem_t2'])) / 2
     return (change_loss + sem_loss) / 2
@@ -38,12 +53,18 @@ def mmcr_loss(sup_criterion, cons_criterion, outputs, batch, alpha: float, cons_
     logits_fusion, logits_s1, logits_s2 = outputs
     is_labeled = batch['is_labeled'].to(logits_fusion.device)
     y = batch['y_change']
-    if cons_loss_type != 'L2' and _fusable(sup_criterion, cons_criterion):
+    l2 = cons_loss_type == 'L2'  # train_semisupervised.py:101-102: the criterion takes sigmoid(logits_s1), not logits_s1
+    if _fusable(sup_criterion, cons_criterion):
         # one fused pass, subsets selected on the device: alpha/3 * (L_f + L_s1 + L_s2)[labelled]
-        # + (1 - alpha) * PJ(logits_s1, sigmoid(logits_s2))[unlabelled]
+        # + (1 - alpha) * L_cons(logits_s1 | sigmoid(logits_s1), sigmoid(logits_s2))[unlabelled]
         a = float(alpha)
-        spec = [(0, 3, a / 3, 1, 0), (1, 3, a / 3, 1, 0), (2, 3, a / 3, 1, 0), (1, 2, 1 - a, 2, 1)]
-        return engine.multi_jaccard(spec, is_labeled, logits_fusion, logits_s1, logits_s2, y)
+        if not l2 and _all_power_jaccard(sup_criterion, cons_criterion):  # the shipped configs: the dedicated kernels
+            spec = [(0, 3, a / 3, 1, 0), (1, 3, a / 3, 1, 0), (2, 3, a / 3, 1, 0), (1, 2, 1 - a, 2, 1)]
+            return engine.multi_jaccard(spec, is_labeled, logits_fusion, logits_s1, logits_s2, y)
+        ks, kc = sup_criterion.kind, cons_criterion.kind
+        spec = [(0, 3, a / 3, 1, 0, ks, 0), (1, 3, a / 3, 1, 0, ks, 0), (2, 3, a / 3, 1, 0, ks, 0),
+                (1, 2, 1 - a, 2, 1, kc, int(l2))]
+        return engine.multi_loss(spec, is_labeled, logits_fusion, logits_s1, logits_s2, y)
     loss = None
     if bool(is_labeled.any()):
         sup = (sup_criterion(logits_fusion[is_labeled], y[is_labeled])
@@ -52,9 +73,8 @@ def mmcr_loss(sup_criterion, cons_criterion, outputs, batch, alpha: float, cons_
         loss = alpha * sup
     if not bool(is_labeled.all()):
         nl = torch.logical_not(is_labeled)
-        if cons_loss_type == 'L2':
-            raise NotImplementedError('L2 consistency loss is not on the MI355X hot path')
-        cons = (1 - alpha) * cons_criterion(logits_s1[nl], torch.sigmoid(logits_s2[nl]))
+        first = torch.sigmoid(logits_s1[nl]) if l2 else logits_s1[nl]
+        cons = (1 - alpha) * cons_criterion(first, torch.sigmoid(logits_s2[nl]))
         loss = cons if loss is None else loss + cons
     return loss
 
@@ -75,6 +95,6 @@ def _step_loss(cfg, outputs, batch):
         return dualtask_loss(crit, crit, outputs, batch)
     if t in ('whatevernet', 'whatevernet2') and isinstance(outputs, (tuple, list)):
         cons_type = cfg.CONSISTENCY_TRAINER.get('LOSS_TYPE', 'PowerJaccardLoss')
-        cons = loss_functions.get_criterion(cons_type) if cons_type != 'L2' else None
+        cons = loss_functions.get_criterion(cons_type)
         return mmcr_loss(crit, cons, outputs, batch, cfg.CONSISTENCY_TRAINER.LOSS_FACTOR, cons_type)
     return supervised_loss(crit, outputs, batch)
