@@ -691,10 +691,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, OCC) void igemm_halo16_x3(I
 
 namespace {
 
-struct H16Cfg {
-    int id, bm, bn;
-};
-
 // 0 = off (the 32x32x16 halo kernel), 1 = automatic tile choice, 2 + id = force tile config id
 // (SCD_TUNE_HALO16_* bits of the launch).
 int halo16_mode(uint32_t tune) {
@@ -731,72 +727,13 @@ int h2_wide_tile(uint32_t tune) { return (tune & SCD_TUNE_H2_TILE_2X2) ? 0 : 1; 
 // waves; same-box A/B 31.81 -> 31.49 ms per step); SCD_TUNE_H2_TILE64_2X2: 2 x 2 waves (config 1).
 int h2_tile64(uint32_t tune) { return (tune & SCD_TUNE_H2_TILE64_2X2) ? 0 : 1; }
 
-// Double buffering where two halo buffers of every resident block still fit the CU's 160 KB of LDS: for x3 / x5 /
-// bf16; h2 runs single-buffered (same-box A/B: data grad -2.3%, step +0.5%).  SCD_TUNE_HALO16_DB_ON / _OFF force it.
-int halo16_db(uint32_t tune, bool h2) {
-    if (tune & SCD_TUNE_HALO16_DB_OFF) return 0;
-    if (tune & SCD_TUNE_HALO16_DB_ON) return 1;
-    return h2 ? 0 : 1;
-}
-
-template <int WM, int WN, int TM, int TN, int OCC, bool DB, int NP, bool WL = false>
-void launch16c(const IgemmArgs &a, int tw, hipStream_t s) {
-    if constexpr (NP == 1) {  // the bf16 arithmetic: fp32 or bf16 storage
-        if (a.sb) {
-            if (a.in_scale)
-                launch16b<WM, WN, TM, TN, OCC, true, DB, NP, true>(a, tw, s);
-            else
-                launch16b<WM, WN, TM, TN, OCC, false, DB, NP, true>(a, tw, s);
-            return;
-        }
-    }
-    if (a.in_scale)
-        launch16b<WM, WN, TM, TN, OCC, true, DB, NP, false, WL>(a, tw, s);
-    else
-        launch16b<WM, WN, TM, TN, OCC, false, DB, NP, false, WL>(a, tw, s);
-}
-
-template <int WM, int WN, int TM, int TN, int OCC>
-void launch16(const IgemmArgs &a, int tw, hipStream_t s) {
-    constexpr int BM = WM * TM * 16;
-    const int hr = (BM / tw + 2) * (tw + 2);
-    const bool db3 = tw != 64 && halo16_db(a.tune, false) && OCC * 2 * 3 * hr * 64 <= 160 * 1024;
-    const bool db_h2 = tw != 64 && halo16_db(a.tune, true) && OCC * 2 * 2 * hr * 64 <= 160 * 1024;
-    // h2 needs the h2 weight split and a bound (igemm_takes_halo16); otherwise x3 (h2 mode: other shapes)
-    const int planes = a.src_bound && h2_weight_format(a.math, a.ntaps, a.c) ? (h2_prescale(a.tune) ? 4 : 2)
-                       : math_planes(a.math) == 2                            ? 3
-                                                                             : math_planes(a.math);
-    switch (planes) {
-        case 1:  // one plane: double buffering always fits
-            if (halo16_db(a.tune, false))
-                launch16c<WM, WN, TM, TN, OCC, true, 1>(a, tw, s);
-            else
-                launch16c<WM, WN, TM, TN, OCC, false, 1>(a, tw, s);
-            break;
-        case 2:
-            if (db_h2)
-                launch16c<WM, WN, TM, TN, OCC, true, 2>(a, tw, s);
-            else
-                launch16c<WM, WN, TM, TN, OCC, false, 2>(a, tw, s);
-            break;
-        case 4:
-            if (db_h2)
-                launch16c<WM, WN, TM, TN, OCC, true, 4>(a, tw, s);
-            else
-                launch16c<WM, WN, TM, TN, OCC, false, 4>(a, tw, s);
-            break;
-        case 5:
-            if (db3)
-                launch16c<WM, WN, TM, TN, OCC, true, 5>(a, tw, s);
-            else
-                launch16c<WM, WN, TM, TN, OCC, false, 5>(a, tw, s);
-            break;
-        default:
-            if (db3)
-                launch16c<WM, WN, TM, TN, OCC, true, 3>(a, tw, s);
-            else
-                launch16c<WM, WN, TM, TN, OCC, false, 3>(a, tw, s);
-    }
+// Double buffering where two halo buffers of every resident block still fit the CU's 160 KB of LDS (halo16_instance):
+// the default for x3 / x5 / bf16; h2 runs single-buffered (same-box A/B: data grad -2.3%, step +0.5%).
+// SCD_TUNE_HALO16_DB_ON / _OFF force it for every tile.
+bool halo16_db(uint32_t tune, bool dflt) {
+    if (tune & SCD_TUNE_HALO16_DB_OFF) return false;
+    if (tune & SCD_TUNE_HALO16_DB_ON) return true;
+    return dflt;
 }
 
 // Tile configurations: id -> (pixels, channels) per block.
@@ -807,23 +744,29 @@ void launch16(const IgemmArgs &a, int tw, hipStream_t s) {
 //   4: 1x2 waves of 128 px x 32 ch (128 x 64),  2 waves/SIMD, h2 only (the same wave tile on 64-channel outputs)
 //   5: 2x2 waves of 128 px x 32 ch (256 x 64),  2 waves/SIMD, h2 only (the wave tile of config 4 on a 16 x 16 pixel
 //      patch, whose halo is 1.27 rows per pixel instead of 1.41: 64-channel sources; SCD_TUNE_H2_TILE64_128 keeps 4)
-constexpr H16Cfg kCfg[] = {{0, 128, 128}, {1, 128, 64}, {2, 64, 128}, {3, 128, 128}, {4, 128, 64}, {5, 256, 64}};
+//
+// The wave layouts igemm_halo16_x3 is built for: WM x WN waves of TM x TN MFMA tiles (16 px x 16 ch each), OCC blocks
+// per SIMD asked for.  ARITH: 0 = every arithmetic (x3, x5, bf16, h2); 4 = h2 with the pre-scaled low term only (NP 4),
+// also with the weight ring; 1 = bf16 only.  Rows 0..5 are the tile configurations above; the 1 x N wave tiles (3..5)
+// run h2 there (bf16 on those measured slower: 21.38 vs 21.05 ms per bf16 step, the 64-channel layers -5..-15%,
+// same-box A/B, round 3; not kept) and bf16 on rows 6..9, at 3 blocks per SIMD.
+struct H16Layout {
+    int wm, wn, tm, tn, occ, arith;
+    constexpr int bm() const { return wm * tm * 16; }  // pixels per block
+    constexpr int bn() const { return wn * tn * 16; }  // channels per block
+};
+constexpr H16Layout kLayout[] = {
+    {2, 2, 4, 4, 2, 0}, {2, 2, 4, 2, 3, 0}, {2, 2, 2, 4, 3, 0},  // configs 0, 1, 2
+    {1, 4, 8, 2, 2, 4}, {1, 2, 8, 2, 2, 4}, {2, 2, 8, 2, 2, 4},  // configs 3, 4, 5: h2
+    {1, 4, 8, 2, 3, 1}, {1, 2, 8, 2, 3, 1}, {2, 2, 8, 2, 3, 1},  // configs 3, 4, 5: bf16
+    {1, 4, 8, 4, 2, 1},  // config 3, bf16: 128 x 256 per block (SCD_HALO16_BF16_TN4 below)
+};
 
-// The 1 x N wave tiles: the h2 arithmetic only (bf16 on them measured slower: 21.38 vs 21.05 ms per bf16 step,
-// the 64-channel layers -5..-15%, same-box A/B, round 3; not kept).
-template <int WM, int WN, int TM, int TN, int OCC>
-void launch16_1xn(const IgemmArgs &a, int tw, hipStream_t s) {
-    constexpr int BM = WM * TM * 16;
-    const int hr = (BM / tw + 2) * (tw + 2);
-    const bool db2 = tw != 64 && halo16_db(a.tune, true) && OCC * 2 * 2 * hr * 64 <= 160 * 1024;
-    if (db2)
-        launch16c<WM, WN, TM, TN, OCC, true, 4>(a, tw, s);
-    else if (halo16_wring(a.tune) && a.ntaps == 9 && tw != 64 && a.n_out % (WN * TN * 16) == 0)  // pieces in the split;
-        // 64-wide tiles: halo + ring would leave one block per CU
-        launch16c<WM, WN, TM, TN, OCC, false, 4, true>(a, tw, s);
-    else
-        launch16c<WM, WN, TM, TN, OCC, false, 4>(a, tw, s);
-}
+// The instance of igemm_halo16_x3 a launch runs: a row of kLayout and the kernel's NP, DB, SB, IN_BN and WL.
+struct H16Inst {
+    int layout, np;
+    bool db, sb, in_bn, wl;
+};
 
 // Whether the 1 x N wave tiles (ids 3, 4) may run: h2 with its weight split, a bound and the pre-scaled low term.
 bool wide_1xn_ok(const IgemmArgs &a) {
@@ -837,25 +780,11 @@ bool bf16_1xn(const IgemmArgs &a) {
     return a.math == SCD_MATH_BF16 && (bool(a.sb) != bool(a.tune & SCD_TUNE_BF16_1XN));
 }
 
-// The 1 x N tiles in the bf16 arithmetic (fp32 or bf16 storage).  Double-buffered halo on the tiles of 128 and more
-// channels; the 64-channel tiles (256 x 64, 128 x 64) single-buffered: there the second buffer cost resident blocks
-// (256 x 64: 41 KB per block, 3 blocks per CU; 5 single-buffered) and every block covers only two to eight 32-channel
-// chunks.  Round 6, tools/perf_conv.py bf16 storage: enc0b fwd 0.516 -> 0.459 ms, up1b 0.236 -> 0.203, enc1a data grad
-// 0.231 -> 0.198 single-buffered, while the 128-channel up3a forward lost 6% (profiles/r06_bf16_halo_db_study.txt).
-// Steps (one process, profiles/r06_bf16_halo_db_ab.txt): dual-stream bs=64 40.29 -> 39.75 ms, MMCR 56.94 -> 56.28,
-// bf16 Siamese 15.17 -> 15.02 (every tile single-buffered: 40.00, 56.49, 15.18).
-// SCD_TUNE_HALO16_DB_ON / _OFF force one choice for every tile.
-template <int WM, int WN, int TM, int TN, int OCC>
-void launch16_1xn_bf16(const IgemmArgs &a, int tw, hipStream_t s) {
-    const bool db = (a.tune & (SCD_TUNE_HALO16_DB_ON | SCD_TUNE_HALO16_DB_OFF)) ? halo16_db(a.tune, false) != 0
-                                                                                  : WN * TN * 16 >= 128;
-    if (db)
-        launch16c<WM, WN, TM, TN, OCC, true, 1>(a, tw, s);
-    else
-        launch16c<WM, WN, TM, TN, OCC, false, 1>(a, tw, s);
-}
-
 }  // namespace
+
+// The tile width tried first: the smallest halo per pixel (180 rows for 128 px).  hip.halo16_tile_width_pref() mirrors
+// it for the tests.
+constexpr int kHalo16PrefTw = 16;
 
 // 0 when `a` does not take this kernel, else 1 + config id; *bm = pixels per tile, *tw = tile width.
 int halo16_pick(const IgemmArgs &a, bool eligible, int *bm, int *tw) {
@@ -884,9 +813,8 @@ int halo16_pick(const IgemmArgs &a, bool eligible, int *bm, int *tw) {
         return 0;
     if (id < 0 || id > 5 || (id > 2 && !wide_1xn_ok(a) && !bf16_1xn(a))) return 0;
     for (;;) {
-        *bm = kCfg[id].bm;
-        const int pref = 16;  // preferred tile width, the smallest halo per pixel (180 rows for 128 px)
-        for (int cand : {pref, 64, 32, 16})
+        *bm = kLayout[id].bm();
+        for (int cand : {kHalo16PrefTw, 64, 32, 16})
             if (a.wo % cand == 0 && a.ho % (*bm / cand) == 0 && *bm / cand >= 1 && *bm % cand == 0) {
                 *tw = cand;
                 return 1 + id;
@@ -905,32 +833,96 @@ int halo16_pick(const IgemmArgs &a, bool eligible, int *bm, int *tw) {
 #ifndef SCD_HALO16_BF16_TN4
 #define SCD_HALO16_BF16_TN4 512
 #endif
-void launch_halo16(const IgemmArgs &a, int cfg, int tw, hipStream_t s) {
-    if (cfg >= 4 && bf16_1xn(a)) {
-        switch (cfg - 1) {
-            case 3:
-                // (automatic tiles only: SCD_TUNE_HALO16_CFG(3) keeps the 128 x 128 tile, the bit-identity tests' A/B)
-                if (SCD_HALO16_BF16_TN4 > 0 && halo16_mode(a.tune) == 1 && a.n_out % 256 == 0 &&
-                    int64_t(a.n_img) * a.ho * a.wo / 128 * (a.n_out / 256) >= SCD_HALO16_BF16_TN4) {
-                    launch16_1xn_bf16<1, 4, 8, 4, 2>(a, tw, s);
-                    return;
-                }
-                launch16_1xn_bf16<1, 4, 8, 2, 3>(a, tw, s);
-                return;
-            case 4: launch16_1xn_bf16<1, 2, 8, 2, 3>(a, tw, s); return;
-            default: launch16_1xn_bf16<2, 2, 8, 2, 3>(a, tw, s); return;
+namespace {
+
+// The 1 x N tiles in the bf16 arithmetic (fp32 or bf16 storage).  Double-buffered halo on the tiles of 128 and more
+// channels; the 64-channel tiles (256 x 64, 128 x 64) single-buffered: there the second buffer cost resident blocks
+// (256 x 64: 41 KB per block, 3 blocks per CU; 5 single-buffered) and every block covers only two to eight 32-channel
+// chunks.  Round 6, tools/perf_conv.py bf16 storage: enc0b fwd 0.516 -> 0.459 ms, up1b 0.236 -> 0.203, enc1a data grad
+// 0.231 -> 0.198 single-buffered, while the 128-channel up3a forward lost 6% (profiles/r06_bf16_halo_db_study.txt).
+// Steps (one process, profiles/r06_bf16_halo_db_ab.txt): dual-stream bs=64 40.29 -> 39.75 ms, MMCR 56.94 -> 56.28,
+// bf16 Siamese 15.17 -> 15.02 (every tile single-buffered: 40.00, 56.49, 15.18).
+// SCD_TUNE_HALO16_DB_ON / _OFF force one choice for every tile.
+//
+// The one place that decides the instance for configuration cfg = halo16_pick's result and tile width tw.
+H16Inst halo16_instance(const IgemmArgs &a, int cfg, int tw) {
+    const int id = cfg - 1;
+    H16Inst k;
+    // h2 needs the h2 weight split and a bound (igemm_takes_halo16); otherwise x3 (h2 mode: other shapes)
+    k.np = a.src_bound && h2_weight_format(a.math, a.ntaps, a.c) ? (h2_prescale(a.tune) ? 4 : 2)
+           : math_planes(a.math) == 2                            ? 3
+                                                                 : math_planes(a.math);
+    // configs 3..5 (halo16_pick: wide_1xn_ok or bf16_1xn) in the bf16 arithmetic: their bf16 rows; config 3 on 256
+    // channels per block where that grid is large enough
+    // (automatic tiles only: SCD_TUNE_HALO16_CFG(3) keeps the 128 x 128 tile, the bit-identity tests' A/B)
+    const bool bf = id >= 3 && bf16_1xn(a);
+    const bool tn4 = SCD_HALO16_BF16_TN4 > 0 && halo16_mode(a.tune) == 1 && a.n_out % 256 == 0 &&
+                     int64_t(a.n_img) * a.ho * a.wo / 128 * (a.n_out / 256) >= SCD_HALO16_BF16_TN4;
+    k.layout = !bf ? (id >= 0 && id <= 5 ? id : 2) : id != 3 ? id + 3 : tn4 ? 9 : 6;
+    const H16Layout &l = kLayout[k.layout];
+    const bool h2 = k.np == 2 || k.np == 4;
+    const int xp = k.np == 1 ? 1 : h2 ? 2 : 3;  // halo planes in LDS
+    // both halo buffers of every resident block within the CU's 160 KB (one plane: always; 64-wide tiles of two and
+    // three planes stay single-buffered)
+    const int hr = (l.bm() / tw + 2) * (tw + 2);
+    const bool fits = xp == 1 || (tw != 64 && l.occ * 2 * xp * hr * 64 <= 160 * 1024);
+    k.db = halo16_db(a.tune, bf ? l.bn() >= 128 : !h2) && fits;
+    k.sb = k.np == 1 && a.sb;  // the bf16 arithmetic: fp32 or bf16 storage
+    k.in_bn = a.in_scale != nullptr;
+    // the weight ring: the h2 1 x N tiles, single-buffered, 9 taps, whole pieces in the split; 64-wide tiles: halo + ring
+    // would leave one block per CU
+    k.wl = l.arith == 4 && !k.db && halo16_wring(a.tune) && a.ntaps == 9 && tw != 64 && a.n_out % l.bn() == 0;
+    return k;
+}
+
+// H16Inst -> template arguments, last step first.  Combinations no launch takes are not built: the weight ring off the
+// h2 1 x N tiles and off 64-wide tiles, bf16 storage off the bf16 arithmetic, the 1 x N tiles in x3 / x5.
+template <int I, int NP, bool DB, bool SB = false, bool WL = false>
+void launch16_bn(const IgemmArgs &a, const H16Inst &k, int tw, hipStream_t s) {
+    constexpr H16Layout L = kLayout[I];
+    if (k.in_bn)
+        launch16b<L.wm, L.wn, L.tm, L.tn, L.occ, true, DB, NP, SB, WL>(a, tw, s);
+    else
+        launch16b<L.wm, L.wn, L.tm, L.tn, L.occ, false, DB, NP, SB, WL>(a, tw, s);
+}
+template <int I, int NP, bool DB>
+void launch16_db(const IgemmArgs &a, const H16Inst &k, int tw, hipStream_t s) {
+    if constexpr (NP == 1)
+        if (k.sb) return launch16_bn<I, NP, DB, true>(a, k, tw, s);
+    if constexpr (kLayout[I].arith == 4 && !DB)
+        if (k.wl) return launch16_bn<I, NP, DB, false, true>(a, k, tw, s);
+    launch16_bn<I, NP, DB>(a, k, tw, s);
+}
+template <int I, int NP>
+void launch16_np(const IgemmArgs &a, const H16Inst &k, int tw, hipStream_t s) {
+    if (k.db)
+        launch16_db<I, NP, true>(a, k, tw, s);
+    else
+        launch16_db<I, NP, false>(a, k, tw, s);
+}
+template <int I = 0>
+void launch16_layout(const IgemmArgs &a, const H16Inst &k, int tw, hipStream_t s) {  // row k.layout, then its arithmetic
+    if constexpr (I < int(sizeof(kLayout) / sizeof(kLayout[0]))) {
+        if (k.layout != I) return launch16_layout<I + 1>(a, k, tw, s);
+        if constexpr (kLayout[I].arith != 0) {
+            launch16_np<I, kLayout[I].arith>(a, k, tw, s);
+        } else {
+            switch (k.np) {
+                case 1: launch16_np<I, 1>(a, k, tw, s); break;
+                case 2: launch16_np<I, 2>(a, k, tw, s); break;
+                case 4: launch16_np<I, 4>(a, k, tw, s); break;
+                case 5: launch16_np<I, 5>(a, k, tw, s); break;
+                default: launch16_np<I, 3>(a, k, tw, s);
+            }
         }
-    }
-    switch (cfg - 1) {
-        case 0: launch16<2, 2, 4, 4, 2>(a, tw, s); break;
-        case 1: launch16<2, 2, 4, 2, 3>(a, tw, s); break;
-        case 3: launch16_1xn<1, 4, 8, 2, 2>(a, tw, s); break;
-        case 4: launch16_1xn<1, 2, 8, 2, 2>(a, tw, s); break;
-        case 5: launch16_1xn<2, 2, 8, 2, 2>(a, tw, s); break;
-        default: launch16<2, 2, 2, 4, 3>(a, tw, s); break;
     }
 }
 
+}  // namespace
+
+void launch_halo16(const IgemmArgs &a, int cfg, int tw, hipStream_t s) {
+    launch16_layout(a, halo16_instance(a, cfg, tw), tw, s);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Halo forward conv of a 16-channel source (the input layer: 5 bands padded to 16).  The 32-deep MFMA step
@@ -1443,6 +1435,56 @@ __device__ __forceinline__ void w16_chain(f32x4 (&acc)[9][W16L<LC>::CB][W16L<LC>
         w16_chain<H + 1, PB, HW_, NP, LC>(acc, dv, f0, f1, xbase);
     }
 }
+
+// The patch of every halo weight grad: 2 x 16 pixels, its X halo 4 x 18.
+constexpr int kW16PH = 2, kW16PW = 16;
+
+// A weight-grad block (wgrad_halo16_x3, wgrad_halo16_dma, wgrad_halo16_c16): its split, ROWS rows r from r0, channel
+// tile ct = COLS channels c from c0 (COLS 16, the 16-channel source: one tile), and its range [pbeg, pend) of the
+// patch walk (pimg = ph_n x pw_n patches per image).  writer (block-uniform): this block stores the dY it forms (RBN
+// with a.rows_out: the blocks of channel tile 0).
+struct W16Block {
+    int split, ct, r0, c0;
+    int pw_n, ph_n, pimg, pbeg, pend;
+    bool writer;
+};
+template <int ROWS, int COLS, bool RBN>
+__device__ __forceinline__ W16Block w16_block(const WgradArgs &a) {
+    W16Block b;
+    const uint32_t per_split = COLS == 16 ? uint32_t(a.grid_r) : uint32_t(a.grid_r * a.grid_j);
+    const uint32_t L = a.remap ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
+    b.split = int(L / per_split);
+    const int rem = int(L - uint32_t(b.split) * per_split);
+    b.ct = COLS == 16 ? 0 : rem / a.grid_r;
+    b.r0 = (rem - b.ct * a.grid_r) * ROWS;
+    b.c0 = b.ct * COLS;
+    b.pw_n = a.wo / kW16PW;
+    b.ph_n = a.ho / kW16PH;
+    b.pimg = b.pw_n * b.ph_n;
+    const int npatch = a.n_img_w * b.pimg;
+    b.pbeg = b.split * a.kchunk;
+    b.pend = min(npatch, b.pbeg + a.kchunk);
+    b.writer = RBN && a.rows_out && b.ct == 0;
+    return b;
+}
+
+// The slab stores of a block, one 16 bytes per tile: acc[t][cb][rb][q] is r = r0w + 16 rb + (lane & 15),
+// c = c0w + 16 cb + 4g + q, where r0w = r0 + 16 NRB wi and c0w = c0 + 16 NCB wj are the wave's first row and channel.
+template <int NCB, int NRB>
+__device__ __forceinline__ void w16_store_slabs(f32x4 (&acc)[9][NCB][NRB], const WgradArgs &a, int split, int r0w, int w16,
+                                                int c0w, int g) {
+    float *slab = a.slabs + size_t(split) * a.R * a.Ng;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+            for (int r = 0; r < NRB; ++r) {
+                const int row = r0w + 16 * r + w16;
+                const int col = c0w + 16 * cb + 4 * g;
+                gstore4(slab + size_t(row) * a.Ng + t * a.C + col, acc[t][cb][r]);
+            }
+}
 }  // namespace
 
 // RG = 2 (LC 1 only): a block of 8 waves owns 128 rows r x 64 channels c; the two 4-wave groups share the
@@ -1459,7 +1501,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
     static_assert(!RBN || (LC == 1 && (NP == 1 || NP == 4)), "rows transform: h2 / bf16, along-c layout");
     constexpr uint32_t EB = SB ? 2u : 4u;
     constexpr int NT = 256 * RG;
-    constexpr int PH = 2, PW = 16, P = PH * PW;
+    constexpr int PH = kW16PH, PW = kW16PW, P = PH * PW;
     constexpr int HW_ = PW + 2, HP = (PH + 2) * HW_;  // halo: 4 x 18
     constexpr int RS = kW16RS;                        // X row stride (64 channels + 32 bytes)
     constexpr int RSD = 128 * RG + 32;                // dY row stride (64 RG rows + 32 bytes: conflict-free reads)
@@ -1490,21 +1532,14 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
     constexpr int NCB = W16L<LC>::CB, NRB = W16L<LC>::RB;
     // wave's dY / X block (in units of its width)
     const int wi = LC ? (RG == 1 ? 0 : wid >> 2) : wid >> 1, wj = LC ? (RG == 1 ? wid : wid & 3) : wid & 1;
-    const uint32_t per_split = uint32_t(a.grid_r * a.grid_j);
-    const uint32_t L = a.remap ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
-    const int split = int(L / per_split);
-    const int rem = int(L - uint32_t(split) * per_split);
-    const int ct = rem / a.grid_r;
-    const int r0 = (rem - ct * a.grid_r) * 64 * RG, c0 = ct * 64;
-    const int pw_n = a.wo / PW, ph_n = a.ho / PH, pimg = pw_n * ph_n;
-    const int npatch = a.n_img_w * pimg;
-    const int pbeg = split * a.kchunk, pend = min(npatch, pbeg + a.kchunk);
+    const W16Block blk = w16_block<RBLK, 64, RBN>(a);
+    const int r0 = blk.r0, c0 = blk.c0, pimg = blk.pimg, pbeg = blk.pbeg, pend = blk.pend;
 
     const __amdgpu_buffer_rsrc_t rs_rows = make_rsrc(a.rows, a.rows_bytes);
     const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(a.src, a.src_bytes);
     const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(RBN ? a.rows_y : a.rows, RBN ? a.y_bytes : 0u);
-    const bool writer = RBN && a.rows_out && ct == 0;  // block-uniform: this block stores its dY pieces
-    float omax = 0.f;                                  // RBN writer: max |dY| stored by this lane
+    const bool writer = blk.writer;  // this block stores its dY pieces
+    float omax = 0.f;                // RBN writer: max |dY| stored by this lane
 
     StageT<SB> ra[A_PER], rb[B_PER], ya[RBN && !YDMA ? A_PER : 1];
     unsigned char *const ystage = smem + STAGE + COEF;  // YDMA: piece e of the patch at e * 16
@@ -1520,7 +1555,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
             x_sh = gload4(a.src_shift + ch);
         }
         x_valid = 0;
-        const int y0 = patch_y0(pr, pw_n, ph_n, PH), x0 = patch_x0(pr, pw_n, ph_n, PW);
+        const int y0 = patch_y0(pr, blk.pw_n, blk.ph_n, PH), x0 = patch_x0(pr, blk.pw_n, blk.ph_n, PW);
         st_img = img;
         st_y0 = y0;
         st_x0 = x0;
@@ -1710,18 +1745,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_x3(WgradArgs a)
                 for (int r = 0; r < NRB; ++r) acc[t][cb][r] *= k;
     }
     if (writer && a.rows_out_bound) wave_max_bound(a.rows_out_bound, omax);  // uniform: the whole block takes part
-    // acc[t][cb][rb][q]: r = r0 + 16 NRB wi + 16rb + (lane & 15), c = c0 + 16 NCB wj + 16cb + 4g + q
-    float *slab = a.slabs + size_t(split) * a.R * a.Ng;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int r = 0; r < NRB; ++r) {
-                const int row = r0 + 16 * NRB * wi + 16 * r + w16;
-                const int col = c0 + 16 * NCB * wj + 16 * cb + 4 * g;
-                gstore4(slab + size_t(row) * a.Ng + t * a.C + col, acc[t][cb][r]);
-            }
+    w16_store_slabs(acc, a, blk.split, r0 + 16 * NRB * wi, w16, c0 + 16 * NCB * wj, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1760,7 +1784,7 @@ constexpr int kDmaSink = 1024;
 template <int RG, int NB, bool XT = false, bool RBN = false>
 __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_dma(WgradArgs a) {
     constexpr int NT = 256 * RG, NW = NT / 64;
-    constexpr int PH = 2, PW = 16, P = PH * PW;
+    constexpr int PH = kW16PH, PW = kW16PW, P = PH * PW;
     constexpr int HW_ = PW + 2, HP = (PH + 2) * HW_;  // halo: 4 x 18
     constexpr int RS = kW16RS;                        // X row stride (64 channels + 32 bytes)
     constexpr int RSD = 128 * RG + 32;                // dY row stride (64 RG rows + 32 bytes)
@@ -1785,17 +1809,10 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_dma(WgradArgs a
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wave_u = __builtin_amdgcn_readfirstlane(wid);
     const int wi = RG == 1 ? 0 : wid >> 2, wj = RG == 1 ? wid : wid & 3;
-    const uint32_t per_split = uint32_t(a.grid_r * a.grid_j);
-    const uint32_t L = a.remap ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
-    const int split = int(L / per_split);
-    const int rem = int(L - uint32_t(split) * per_split);
-    const int ct = rem / a.grid_r;
-    const int r0 = (rem - ct * a.grid_r) * 64 * RG, c0 = ct * 64;
-    const int pw_n = a.wo / PW, ph_n = a.ho / PH, pimg = pw_n * ph_n;
-    const int npatch = a.n_img_w * pimg;
-    const int pbeg = split * a.kchunk, pend = min(npatch, pbeg + a.kchunk);
-    const bool writer = RBN && a.rows_out && ct == 0;  // block-uniform: this block stores the formed dY
-    float omax = 0.f;                                  // writer: max |dY| stored by this thread
+    const W16Block blk = w16_block<RBLK, 64, RBN>(a);
+    const int r0 = blk.r0, c0 = blk.c0, pimg = blk.pimg, pbeg = blk.pbeg, pend = blk.pend;
+    const bool writer = blk.writer;  // this block stores the formed dY
+    float omax = 0.f;                // writer: max |dY| stored by this thread
 
     const __amdgpu_buffer_rsrc_t rs_rows = make_rsrc(a.rows, a.rows_bytes);
     const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(a.src, a.src_bytes);
@@ -1840,7 +1857,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_dma(WgradArgs a
     };
     auto cursor_at = [&](int pi) {
         const int img = pi / pimg, pr = pi - img * pimg;
-        return Cursor{img, patch_y0(pr, pw_n, ph_n, PH), patch_x0(pr, pw_n, ph_n, PW)};
+        return Cursor{img, patch_y0(pr, blk.pw_n, blk.ph_n, PH), patch_x0(pr, blk.pw_n, blk.ph_n, PW)};
     };
     auto advance = [&](Cursor &c) {
         if constexpr (SCD_WGRAD_ROW_WALK) {
@@ -2079,18 +2096,7 @@ __global__ __launch_bounds__(256 * RG, 2 / RG) void wgrad_halo16_dma(WgradArgs a
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (writer && a.rows_out_bound) wave_max_bound(a.rows_out_bound, omax);  // uniform: the whole block takes part
-
-    float *slab = a.slabs + size_t(split) * a.R * a.Ng;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int r = 0; r < NRB; ++r) {
-                const int row = r0 + 16 * NRB * wi + 16 * r + w16;
-                const int col = c0 + 16 * NCB * wj + 16 * cb + 4 * g;
-                gstore4(slab + size_t(row) * a.Ng + t * a.C + col, acc[t][cb][r]);
-            }
+    w16_store_slabs(acc, a, blk.split, r0 + 16 * NRB * wi, w16, c0 + 16 * NCB * wj, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2172,7 +2178,7 @@ template <int NP, bool RBN, bool SB = false>
 __global__ __launch_bounds__(256, 2) void wgrad_halo16_c16(WgradArgs a) {
     static_assert(!SB || NP == 1, "bf16 storage runs the bf16 arithmetic");
     constexpr uint32_t EB = SB ? 2u : 4u;
-    constexpr int PH = 2, PW = 16, P = PH * PW;
+    constexpr int PH = kW16PH, PW = kW16PW, P = PH * PW;
     constexpr int HW_ = PW + 2, HP = (PH + 2) * HW_;  // halo: 4 x 18
     constexpr int RS = kW16RS, RSX = kC16RS;
     constexpr int PA = P * RS, PB = HP * RSX;           // plane bytes
@@ -2190,12 +2196,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo16_c16(WgradArgs a) {
     }
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const uint32_t L = a.remap ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
-    const int split = int(L / uint32_t(a.grid_r));
-    const int r0 = int(L - uint32_t(split) * uint32_t(a.grid_r)) * 64;
-    const int pw_n = a.wo / PW, ph_n = a.ho / PH, pimg = pw_n * ph_n;
-    const int npatch = a.n_img_w * pimg;
-    const int pbeg = split * a.kchunk, pend = min(npatch, pbeg + a.kchunk);
+    const W16Block blk = w16_block<64, 16, false>(a);  // (no block of this kernel stores the dY it forms)
+    const int r0 = blk.r0, pimg = blk.pimg, pbeg = blk.pbeg, pend = blk.pend;
 
     const __amdgpu_buffer_rsrc_t rs_rows = make_rsrc(a.rows, a.rows_bytes);
     const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(a.src, a.src_bytes);
@@ -2224,7 +2226,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo16_c16(WgradArgs a) {
             r_mul = (a.rbn_gamma ? gload4(a.rbn_gamma + c) : f32x4{1.f, 1.f, 1.f, 1.f}) * r_iv;
         }
         x_valid = 0;
-        const int y0 = patch_y0(pr, pw_n, ph_n, PH), x0 = patch_x0(pr, pw_n, ph_n, PW);
+        const int y0 = patch_y0(pr, blk.pw_n, blk.ph_n, PH), x0 = patch_x0(pr, blk.pw_n, blk.ph_n, PW);
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             const int e = tid + i * 256, q = e >> 4, cq = e & 15;
@@ -2364,7 +2366,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo16_c16(WgradArgs a) {
         for (int t = 0; t < 9; ++t) acc[t] *= k;
     }
     // acc[t][q]: r = r0 + 16 wid + (lane & 15), c = 4g + q
-    float *slab = a.slabs + size_t(split) * a.R * a.Ng;
+    float *slab = a.slabs + size_t(blk.split) * a.R * a.Ng;
     const int row = r0 + 16 * wid + w16;
 #pragma unroll
     for (int t = 0; t < 9; ++t) gstore4(slab + size_t(row) * a.Ng + t * 16 + 4 * g, acc[t]);

@@ -544,7 +544,7 @@ def set_halo16(mode: int) -> int:
 
 
 def halo16_tile_width_pref() -> int:
-    """The tile width the 16x16x32 halo kernel tries first (halo16_pick in conv_halo16.hip)."""
+    """The tile width the 16x16x32 halo kernel tries first: mirrors kHalo16PrefTw in conv_halo16.hip."""
     return 16
 
 

@@ -408,10 +408,12 @@ def test_fused_input_bn(dev, n, h, w, ci, co, nseg):
         hip.set_conv_math(prev_m)
 
 
-@pytest.mark.parametrize('n,h,w,ci,co,nseg', [(4, 16, 32, 128, 64, 2), (2, 32, 16, 64, 128, 1), (4, 8, 16, 256, 96, 2)])
+@pytest.mark.parametrize('n,h,w,ci,co,nseg', [(4, 16, 32, 128, 64, 2), (2, 32, 16, 64, 128, 1), (4, 8, 16, 256, 96, 2),
+                                              (2, 4, 32, 64, 96, 1), (2, 2, 64, 64, 96, 1)])
 def test_fused_bn_backward_partials(dev, n, h, w, ci, co, nseg):
     """Data-grad conv with BatchNorm-backward partial sums in its epilogue + bn_relu_backward_tiles == the conv
-    followed by bn_relu_backward's own partial pass (dy, dgamma, dbeta, conv-bias grad)."""
+    followed by bn_relu_backward's own partial pass (dy, dgamma, dbeta, conv-bias grad).  The 4 x 32 and 2 x 64 maps
+    take the 128 x 64 tile at widths 32 and 64, with its second channel block half empty."""
     from multimodal_siamese_cd_amd import hip
     prev_m = hip.set_conv_math('x3')
     try:
