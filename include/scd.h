@@ -156,8 +156,10 @@ enum scd_conv_math {
  *      Still 9 (no layout or signature change): three tune selectors were withdrawn with their kernels, all measured
  *      slower -- the late halo load (bit 27), the warp-specialized h2 tiles (bit 29) and the double-buffered h2
  *      weight grad (bit 31).
- *  10: the loss family appended (scd_loss_kind_t, scd_loss_term_t, scd_loss_multi_*); nothing existing changes. */
-#define SCD_ABI_VERSION 10
+ *  10: the loss family appended (scd_loss_kind_t, scd_loss_term_t, scd_loss_multi_*); nothing existing changes.
+ *  11: scd_igemm_kernel (scd_igemm_kernel_t, enum scd_igemm_family): the kernel instance of a conv launch, a host
+ *      query; nothing existing changes and no kernel does. */
+#define SCD_ABI_VERSION 11
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
  * the shape or the missing operand bounds keep the conv off the requested kernels); negative = invalid descriptor.
@@ -306,6 +308,38 @@ int scd_igemm_input_bn_supported(const scd_igemm_t *d);
 /* Number of statistic tiles scd_conv_igemm would write for `d` (0: no fused statistics for this shape or
  * arithmetic, use scd_bn_train_stats); *tile_pixels receives the pixels per tile. */
 int scd_igemm_stat_tiles(const scd_igemm_t *d, int32_t *tile_pixels);
+
+/* ABI 11: the kernel instance scd_conv_igemm would run for `d` -- the family and, for the 16x16x32 halo kernel, the
+ * wave layout and the template switches the dispatcher chose.  Decided by the code the launch itself follows (one
+ * function picks, the launch and this query both read its answer).  Host only: no device is initialised and no pointer
+ * of the descriptor is dereferenced (their alignment is read), so a test can pin the dispatcher's rules on a machine
+ * without a GPU and a GPU test can assert which instance it is about to check.  Returns 0, or the error scd_conv_igemm
+ * would report for `d` before launching.  A conv run as several launches over image ranges (operands of 2 GiB and
+ * more) reports its first launch. */
+enum scd_igemm_family {
+    SCD_KERNEL_F32 = 0,        /* fp32 MFMA, per-tap gather                                                     */
+    SCD_KERNEL_X3 = 1,         /* 32x32x16 split-bf16 MFMA, per-tap gather                                      */
+    SCD_KERNEL_HALO32 = 2,     /* 32x32x16 split-bf16 MFMA on a staged halo (3x3)                               */
+    SCD_KERNEL_HALO16 = 3,     /* igemm_halo16_x3: 16x16x32 MFMA on a staged halo (3x3, src.c % 32 == 0)        */
+    SCD_KERNEL_HALO16_C16 = 4, /* igemm_halo16_c16: the 16-channel source (input layer)                         */
+    SCD_KERNEL_GATHER16 = 5    /* igemm_gather16: 1- / 4-tap convs (ConvTranspose forward / data grad)          */
+};
+typedef struct scd_igemm_kernel {
+    int32_t family;         /* enum scd_igemm_family */
+    int32_t layout;         /* SCD_KERNEL_HALO16: the wave-layout row (0..2 the 2x2 tiles of every arithmetic, 3..5 the
+                               h2 1xN tiles 128x128 / 128x64 / 256x64, 6..8 the same under bf16, 9 bf16 128x256);
+                               -1 for the other families */
+    int32_t block_pixels;   /* output pixels per workgroup (the record tile of stat_rec / bn_bwd on the halo kernels) */
+    int32_t block_channels; /* output channels per workgroup */
+    int32_t tile_width;     /* halo kernels: the tile is block_pixels / tile_width rows of tile_width pixels; else 0 */
+    int32_t np;             /* arithmetic planes: 1 bf16, 3 x3, 5 x5, 4 h2 (2: h2 without the pre-scaled low term),
+                               0 the fp32 MFMA */
+    int32_t db;             /* double-buffered halo */
+    int32_t sb;             /* bf16 storage */
+    int32_t in_bn;          /* fused input BatchNorm-apply + ReLU */
+    int32_t wl;             /* weights through the LDS ring */
+} scd_igemm_kernel_t;
+int scd_igemm_kernel(const scd_igemm_t *d, scd_igemm_kernel_t *out);
 
 /* ---------------------------------------------------------------------------------------------
  * Weight gradient (split-K implicit GEMM on MFMA), deterministic two-stage reduction.

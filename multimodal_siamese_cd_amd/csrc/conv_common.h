@@ -127,9 +127,27 @@ struct WgradArgs {
     float *colsum;
 };
 
-// Split-bf16 ("x3") launchers, conv_x3.hip.  Return false when the shape is not supported by the x3 kernels
-// (the caller then runs the fp32-MFMA kernel).
-bool launch_igemm_x3(const IgemmArgs &a, hipStream_t s);
+// The kernel instance a launch runs (the fields of scd_igemm_kernel_t).  launch_igemm_x3 and scd_conv_igemm's fp32
+// branch launch what igemm_x3_choose / igemm_decide (conv_f32.hip) fill in, and the scd_igemm_kernel query reports the
+// same struct: one decision, two readers.
+struct IgemmChoice {
+    int family;  // enum scd_igemm_family
+    int cfg;     // the family's pick result: halo16_pick / gather16_pick / halo_pick value, or the generic tile id
+    int bm, bn;  // pixels and channels per block
+    int tw;      // tile width (halo kernels; 0 otherwise)
+    int layout;  // halo16: row of kLayout; -1 otherwise
+    int np;      // arithmetic planes (1 bf16, 3 x3, 5 x5, 2 / 4 h2; 0 fp32 MFMA)
+    int db, sb, in_bn, wl;
+};
+// conv_x3.hip: false when no split-arithmetic kernel takes `a` (the caller's fp32 kernels, or none for bf16 views).
+bool igemm_x3_choose(const IgemmArgs &a, IgemmChoice &k);
+// The instance each 16x16x32 family runs for its pick result (conv_halo16.hip, conv_gather16.hip).
+void halo16_describe(const IgemmArgs &a, int cfg, int tw, IgemmChoice &k);
+void halo16_c16_describe(const IgemmArgs &a, int tw, IgemmChoice &k);
+void gather16_describe(const IgemmArgs &a, int cfg, IgemmChoice &k);
+
+// Split-bf16 ("x3") launchers, conv_x3.hip.  launch_igemm_x3 runs the kernel igemm_x3_choose returned for `a`.
+void launch_igemm_x3(const IgemmArgs &a, const IgemmChoice &k, hipStream_t s);
 // Tiles (and pixels per tile) of the halo path for `a`, or 0 when `a` does not take it.
 int halo_stat_tiles(const IgemmArgs &a, int *tile_pixels);
 // 16x16x32-MFMA halo igemm (conv_halo16.hip): 0 when `a` does not take it, else its config; launcher.

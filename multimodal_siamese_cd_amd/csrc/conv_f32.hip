@@ -815,9 +815,9 @@ extern "C" int scd_conv_igemm(const scd_igemm_t *d, scd_stream_t stream) {
 }
 
 namespace scd {
-static int conv_igemm_run(const scd_igemm_t *d, hipStream_t s, int bb_ntiles_total) {
-    IgemmArgs a;
-    SCD_TRY(igemm_prepare(d, a));
+// The checks of the optional epilogue forms and the kernel `a` runs: everything scd_conv_igemm decides before it
+// launches, shared with the scd_igemm_kernel query.  *split: launch_igemm_x3 takes the launch (else the fp32 kernels).
+static int igemm_decide(const scd_igemm_t *d, IgemmArgs &a, int bb_ntiles_total, IgemmChoice &k, bool *split) {
     if (d->stat_rec) {
         int tp = 0;
         if (halo_stat_tiles(a, &tp) == 0) {
@@ -845,7 +845,8 @@ static int conv_igemm_run(const scd_igemm_t *d, hipStream_t s, int bb_ntiles_tot
                   "(ConvTranspose store_mode 1 convs take it on every split-bf16 kernel)");
         return SCD_ERR_ARG;
     }
-    if (math_split(a.math) && launch_igemm_x3(a, s)) return launch_status("scd_conv_igemm");
+    *split = math_split(a.math) && igemm_x3_choose(a, k);
+    if (*split) return SCD_OK;
     if (a.sb) {
         set_error("igemm: bf16 views need the bf16 halo16 / c16 / gather16 kernels; this shape takes none "
                   "(check scd_igemm_arith): n=%d c=%d %dx%d -> %dx%d n_out=%d ldc=%d taps=%d stride=%d store=%d "
@@ -860,15 +861,60 @@ static int conv_igemm_run(const scd_igemm_t *d, hipStream_t s, int bb_ntiles_tot
         set_error("igemm: dst_bound needs the split-bf16 kernels (math x3 / h2 and src.c %% 16 == 0)");
         return SCD_ERR_ARG;
     }
-    if (d->n_out >= 128)
-        launch_igemm_bk<2, 2, 2, 2>(a, s);  // 128 x 128
-    else if (d->n_out >= 64)
-        launch_igemm_bk<4, 1, 2, 2>(a, s);  // 256 x 64
+    // the fp32-MFMA kernels: 128 x 128, 256 x 64 or 256 x 32 per block by n_out
+    k.family = SCD_KERNEL_F32;
+    k.cfg = d->n_out >= 128 ? 1 : d->n_out >= 64 ? 2 : 3;
+    k.bm = k.cfg == 1 ? 128 : 256;
+    k.bn = k.cfg == 1 ? 128 : k.cfg == 2 ? 64 : 32;
+    k.tw = 0;
+    k.layout = -1;
+    k.np = k.db = k.sb = k.in_bn = k.wl = 0;
+    return SCD_OK;
+}
+
+static int conv_igemm_run(const scd_igemm_t *d, hipStream_t s, int bb_ntiles_total) {
+    IgemmArgs a;
+    SCD_TRY(igemm_prepare(d, a));
+    IgemmChoice k;
+    bool split = false;
+    SCD_TRY(igemm_decide(d, a, bb_ntiles_total, k, &split));
+    if (split)
+        launch_igemm_x3(a, k, s);
+    else if (k.cfg == 1)
+        launch_igemm_bk<2, 2, 2, 2>(a, s);
+    else if (k.cfg == 2)
+        launch_igemm_bk<4, 1, 2, 2>(a, s);
     else
-        launch_igemm_bk<4, 1, 2, 1>(a, s);  // 256 x 32
+        launch_igemm_bk<4, 1, 2, 1>(a, s);
     return launch_status("scd_conv_igemm");
 }
 }  // namespace scd
+
+extern "C" int scd_igemm_kernel(const scd_igemm_t *d, scd_igemm_kernel_t *out) {
+    clear_error();
+    if (!d || !out) {
+        set_error("scd_igemm_kernel: null argument");
+        return SCD_ERR_ARG;
+    }
+    IgemmArgs a;
+    SCD_TRY(igemm_query_prepare(d, a));
+    const int chunk = igemm_chunk(d);
+    if (chunk > 0 && chunk < d->src.n) a.n_img = chunk;  // a conv run in image chunks: the first launch's instance
+    IgemmChoice k;
+    bool split = false;
+    SCD_TRY(igemm_decide(d, a, 0, k, &split));
+    out->family = k.family;
+    out->layout = k.layout;
+    out->block_pixels = k.bm;
+    out->block_channels = k.bn;
+    out->tile_width = k.tw;
+    out->np = k.np;
+    out->db = k.db;
+    out->sb = k.sb;
+    out->in_bn = k.in_bn;
+    out->wl = k.wl;
+    return SCD_OK;
+}
 
 namespace scd {
 struct WgradTile {

@@ -300,6 +300,21 @@ int gather16_pick(const IgemmArgs &a) {
     return big >= 512 ? 1 : 3;  // 64 x 128 when 128 x 128 tiles leave CUs idle (two blocks per CU)
 }
 
+// What launch_gather16 runs for cfg (scd_igemm_kernel): the tile of the switch below, h2 or bf16 as launch_g16_math.
+void gather16_describe(const IgemmArgs &a, int cfg, IgemmChoice &k) {
+    k.family = SCD_KERNEL_GATHER16;
+    k.cfg = cfg;
+    k.layout = -1;
+    k.bm = cfg - 1 == 0 || cfg - 1 == 1 ? 128 : 64;
+    k.bn = cfg - 1 == 1 ? 64 : 128;
+    k.tw = 0;
+    k.np = gather16_h2(a) ? 4 : 1;
+    k.db = 0;
+    k.sb = k.np == 1 && a.sb;
+    k.in_bn = 0;
+    k.wl = 0;
+}
+
 void launch_gather16(const IgemmArgs &a, int cfg, hipStream_t s) {
     switch (cfg - 1) {
         case 0: launch_g16_math<2, 2, 4, 4, 2>(a, s); break;

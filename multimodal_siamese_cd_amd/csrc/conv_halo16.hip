@@ -924,6 +924,22 @@ void launch_halo16(const IgemmArgs &a, int cfg, int tw, hipStream_t s) {
     launch16_layout(a, halo16_instance(a, cfg, tw), tw, s);
 }
 
+// What launch_halo16 runs for (cfg, tw), as scd_igemm_kernel reports it: the same halo16_instance call.
+void halo16_describe(const IgemmArgs &a, int cfg, int tw, IgemmChoice &k) {
+    const H16Inst i = halo16_instance(a, cfg, tw);
+    k.family = SCD_KERNEL_HALO16;
+    k.cfg = cfg;
+    k.layout = i.layout;
+    k.bm = kLayout[i.layout].bm();
+    k.bn = kLayout[i.layout].bn();
+    k.tw = tw;
+    k.np = i.np;
+    k.db = i.db;
+    k.sb = i.sb;
+    k.in_bn = i.in_bn;
+    k.wl = i.wl;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Halo forward conv of a 16-channel source (the input layer: 5 bands padded to 16).  The 32-deep MFMA step
 // of igemm_halo16_x3 would be half padding here, so one step covers two taps instead: lane group g supplies
@@ -1228,6 +1244,21 @@ int halo16_c16_pick(const IgemmArgs &a, bool eligible, int *bm, int *tw) {
 static int c16_planes(const IgemmArgs &b) {
     if (math_planes(b.math) == 2) return b.src_bound && h2_weight_format(b.math, 9, 16) ? 4 : 3;
     return math_planes(b.math);
+}
+
+// What launch_halo16_c16 runs (scd_igemm_kernel): 2 x 2 waves of 64 px x 32 ch, single halo buffer.
+void halo16_c16_describe(const IgemmArgs &a, int tw, IgemmChoice &k) {
+    k.family = SCD_KERNEL_HALO16_C16;
+    k.cfg = 1;
+    k.layout = -1;
+    k.bm = 128;
+    k.bn = 64;
+    k.tw = tw;
+    k.np = c16_planes(a);
+    k.db = 0;
+    k.sb = k.np == 1 && a.sb;
+    k.in_bn = 0;
+    k.wl = 0;
 }
 
 template <int TW>

@@ -609,45 +609,71 @@ int halo_stat_tiles(const IgemmArgs &a0, int *tile_pixels) {
     return a.n_img * (a.ho * a.wo / bm);
 }
 
-bool launch_igemm_x3(const IgemmArgs &a0, hipStream_t s) {
+// The kernel of the split arithmetics for `a0`, in the order the families are tried; launch_igemm_x3 launches what
+// this returned and scd_igemm_kernel reports it.
+bool igemm_x3_choose(const IgemmArgs &a0, IgemmChoice &k) {
     if (a0.c % 16) return false;
     const IgemmArgs a = x3_view(a0);
     int bm = 0, tw = 0;
     if (const int c16 = halo16_pick(a, halo_eligible(a), &bm, &tw)) {
-        launch_halo16(a, c16, tw, s);
+        halo16_describe(a, c16, tw, k);
         return true;
     }
     if (const int g16 = gather16_pick(a)) {
-        launch_gather16(a, g16, s);
+        gather16_describe(a, g16, k);
         return true;
     }
     if (halo16_c16_pick(a, halo_eligible(a), &bm, &tw)) {
-        launch_halo16_c16(a, tw, s);
+        halo16_c16_describe(a, tw, k);
         return true;
     }
     if (a.sb) return false;  // bf16 storage: only the bf16 kernels above (the caller reports the unsupported shape)
-    switch (halo_pick(a, &bm, &tw)) {
-        case 1: launch_halo<2, 2, 2, 2>(a, tw, s); return true;
-        case 2: launch_halo<4, 1, 2, 2>(a, tw, s); return true;
-        case 3: launch_halo<4, 1, 2, 1>(a, tw, s); return true;
-        default: break;
+    k.layout = -1;
+    k.np = 3;  // the 32x32x16 kernels run the exact three-way split whatever the mode
+    k.db = k.sb = k.in_bn = k.wl = 0;
+    if (const int h = halo_pick(a, &bm, &tw)) {  // 1 = <2,2,2,2>, 2 = <4,1,2,2>, 3 = <4,1,2,1>
+        k.family = SCD_KERNEL_HALO32;
+        k.cfg = h;
+        k.bm = bm;
+        k.bn = h == 1 ? 128 : h == 2 ? 64 : 32;
+        k.tw = tw;
+        return true;
     }
     // SCD_TUNE_X3_TILE (tile study, tools/perf_convT.py): 1 128x128, 2 256x64, 3 256x32, 4 128x64, 5 256x128
-    switch ((a.tune & SCD_TUNE_X3_TILE_MASK) >> 12) {
-        case 1: launch_x3<2, 2, 2, 2>(a, s); return true;
-        case 2: launch_x3<4, 1, 2, 2>(a, s); return true;
-        case 3: launch_x3<4, 1, 2, 1>(a, s); return true;
-        case 4: launch_x3<2, 2, 2, 1>(a, s); return true;
-        case 5: launch_x3<4, 2, 2, 2>(a, s); return true;
+    int t = int((a.tune & SCD_TUNE_X3_TILE_MASK) >> 12);
+    if (t < 1 || t > 5)
+        t = a.n_out >= 128 ? 1   // 128 x 128
+            : a.n_out >= 64 ? 4  // 128 x 64 (tools/perf_convT.py: up1 ConvT data grad 177 -> 155 us vs 256 x 64)
+                            : 3;  // 256 x 32
+    k.family = SCD_KERNEL_X3;
+    k.cfg = t;
+    k.bm = t == 1 || t == 4 ? 128 : 256;
+    k.bn = t == 1 || t == 5 ? 128 : t == 3 ? 32 : 64;
+    k.tw = 0;
+    return true;
+}
+
+void launch_igemm_x3(const IgemmArgs &a0, const IgemmChoice &k, hipStream_t s) {
+    const IgemmArgs a = x3_view(a0);
+    switch (k.family) {
+        case SCD_KERNEL_HALO16: return launch_halo16(a, k.cfg, k.tw, s);
+        case SCD_KERNEL_GATHER16: return launch_gather16(a, k.cfg, s);
+        case SCD_KERNEL_HALO16_C16: return launch_halo16_c16(a, k.tw, s);
+        case SCD_KERNEL_HALO32:
+            switch (k.cfg) {
+                case 1: return launch_halo<2, 2, 2, 2>(a, k.tw, s);
+                case 2: return launch_halo<4, 1, 2, 2>(a, k.tw, s);
+                default: return launch_halo<4, 1, 2, 1>(a, k.tw, s);
+            }
         default: break;
     }
-    if (a.n_out >= 128)
-        launch_x3<2, 2, 2, 2>(a, s);  // 128 x 128
-    else if (a.n_out >= 64)
-        launch_x3<2, 2, 2, 1>(a, s);  // 128 x 64 (tools/perf_convT.py: up1 ConvT data grad 177 -> 155 us vs 256 x 64)
-    else
-        launch_x3<4, 1, 2, 1>(a, s);  // 256 x 32
-    return true;
+    switch (k.cfg) {
+        case 1: launch_x3<2, 2, 2, 2>(a, s); break;
+        case 2: launch_x3<4, 1, 2, 2>(a, s); break;
+        case 3: launch_x3<4, 1, 2, 1>(a, s); break;
+        case 4: launch_x3<2, 2, 2, 1>(a, s); break;
+        default: launch_x3<4, 2, 2, 2>(a, s); break;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

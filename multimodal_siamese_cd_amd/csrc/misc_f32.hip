@@ -716,7 +716,7 @@ __global__ void pjaccard_bwd_kernel(const float *__restrict__ logits, const floa
 using namespace scd;
 
 // ------------------------------------------------------------------------------------------------
-extern "C" const char *scd_version(void) { return "libscd 0.10.0 (gfx950, ABI 10: the fused multi-term loss family)"; }
+extern "C" const char *scd_version(void) { return "libscd 0.11.0 (gfx950, ABI 11: the conv kernel-instance query)"; }
 extern "C" const char *scd_last_error(void) { return g_err.c_str(); }
 
 extern "C" int scd_device_check(int device) {

@@ -6,6 +6,7 @@ is no fallback: if the library is missing or the device is not gfx950 the first 
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import contextvars
 import ctypes
@@ -64,6 +65,14 @@ class IGEMM(ctypes.Structure):
     ]
 
 
+class IGEMMKERNEL(ctypes.Structure):
+    """scd_igemm_kernel_t (ABI 11): the kernel instance scd_conv_igemm runs for a descriptor."""
+
+    _fields_ = [("family", c_int32), ("layout", c_int32), ("block_pixels", c_int32), ("block_channels", c_int32),
+                ("tile_width", c_int32), ("np", c_int32), ("db", c_int32), ("sb", c_int32), ("in_bn", c_int32),
+                ("wl", c_int32)]
+
+
 class WGRAD(ctypes.Structure):
     _fields_ = [
         ("rows", NHWC),
@@ -120,6 +129,7 @@ _SIGS = {
     "scd_absmax_bound": ([NHWC, c_int32, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "scd_conv_igemm": ([POINTER(IGEMM), c_void_p], c_int),
     "scd_igemm_arith": ([POINTER(IGEMM)], c_int),
+    "scd_igemm_kernel": ([POINTER(IGEMM), POINTER(IGEMMKERNEL)], c_int),
     "scd_igemm_input_bn_supported": ([POINTER(IGEMM)], c_int),
     "scd_igemm_bn_bwd_tiles": ([POINTER(IGEMM), POINTER(c_int32)], c_int),
     "scd_wgrad_src_bn_supported": ([POINTER(WGRAD)], c_int),
@@ -214,7 +224,7 @@ _SIGS = {
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
-ABI_VERSION = 10  # SCD_ABI_VERSION of include/scd.h
+ABI_VERSION = 11  # SCD_ABI_VERSION of include/scd.h
 
 
 def load_library(path: str = LIB_PATH):
@@ -594,6 +604,29 @@ def igemm_arith(src: NHWC, out_h: int, out_w: int, stride: int, taps, wpk: torch
     rc = lib().scd_igemm_arith(ctypes.byref(d))
     _check(min(rc, 0), "scd_igemm_arith")
     return _MATH_BY_ID[rc]
+
+
+# enum scd_igemm_family
+KERNEL_FAMILIES = ('f32', 'x3', 'halo32', 'halo16', 'halo16_c16', 'gather16')
+IgemmKernel = collections.namedtuple(
+    'IgemmKernel', 'family layout block_pixels block_channels tile_width np db sb in_bn wl')
+
+
+def igemm_kernel_of(d: 'IGEMM') -> IgemmKernel:
+    """scd_igemm_kernel for a built descriptor: the instance scd_conv_igemm would run (host only, no device work)."""
+    k = IGEMMKERNEL()
+    _check(lib().scd_igemm_kernel(ctypes.byref(d), ctypes.byref(k)), "scd_igemm_kernel")
+    return IgemmKernel(KERNEL_FAMILIES[k.family], k.layout, k.block_pixels, k.block_channels, k.tile_width, k.np,
+                       bool(k.db), bool(k.sb), bool(k.in_bn), bool(k.wl))
+
+
+def igemm_kernel(src: NHWC, out_h: int, out_w: int, stride: int, taps, wpk: torch.Tensor, n_out: int, bias,
+                 dst: NHWC, store_mode: int = 0, stat_rec=None, in_bn=None, bn_bwd=None, src_bound=None,
+                 dst_bound=None, dst_bound_seed=None) -> IgemmKernel:
+    """The kernel instance conv_igemm would run for the same arguments (family, halo16 layout row, pixels and channels
+    per block, tile width, NP, DB, SB, IN_BN, WL), decided by the code path of the launch."""
+    return igemm_kernel_of(_igemm_desc(src, out_h, out_w, stride, taps, wpk, n_out, bias, dst, store_mode, stat_rec,
+                                       in_bn, bn_bwd, src_bound, dst_bound, dst_bound_seed))
 
 
 def wgrad_arith(d: 'WGRAD') -> str:

@@ -55,8 +55,8 @@ def test_registry_names_that_stay_off():
 
 def test_abi_version(lib):
     from multimodal_siamese_cd_amd import hip
-    assert lib.scd_abi_version() == 10 == hip.ABI_VERSION
-    assert 'ABI 10' in hip.version()
+    assert lib.scd_abi_version() == 11 == hip.ABI_VERSION
+    assert 'ABI 11' in hip.version()
 
 
 def test_term_struct_layout_matches_c_compiler(tmp_path):
