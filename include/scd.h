@@ -158,7 +158,9 @@ enum scd_conv_math {
  *      weight grad (bit 31).
  *  10: the loss family appended (scd_loss_kind_t, scd_loss_term_t, scd_loss_multi_*); nothing existing changes.
  *  11: scd_igemm_kernel (scd_igemm_kernel_t, enum scd_igemm_family): the kernel instance of a conv launch, a host
- *      query; nothing existing changes and no kernel does. */
+ *      query; nothing existing changes and no kernel does.
+ *      Still 11 (symbols appended, nothing existing changes): scd_bn_frozen_coeffs and scd_bn_relu_backward_desc
+ *      (scd_bn_bwd_t, SCD_BN_BWD_FROZEN), the backward through a BatchNorm that uses its running statistics. */
 #define SCD_ABI_VERSION 11
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
@@ -526,6 +528,60 @@ int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const f
                               const float *tile_rec, int32_t ntiles, float *coef, float *dgamma, float *dbeta,
                               float *dbias_prev, const float *da_bound, float *dy_bound, void *ws, size_t ws_bytes,
                               scd_stream_t stream);
+
+/* A BatchNorm that normalises with its running statistics while its parameters train (a module in eval mode inside
+ * a training step: fine-tuning with frozen BatchNorm).  With m = running_mean, r = 1/sqrt(running_var + eps):
+ *   scale = gamma*r, shift = beta - m*scale (as scd_bn_eval_coeffs); a = relu(scale*y + shift)
+ *   dz = da * [scale*y + shift > 0]; dy = scale*dz; dbeta = sum dz; dgamma = sum dz*(y - m)*r
+ *   conv bias in front: sum dy = scale*dbeta -- a true, non-zero gradient, unlike in train mode.
+ * That is scd_bn_relu_backward's dy = gamma*invstd*(dz - k1 - xhat*k2) with k1 = k2 = 0 and (m, r) for the batch's
+ * (mean, invstd): the sums, the conv-epilogue tile records (scd_bn_bwd_tiles_t) and the weight grad that forms dy
+ * from coef (scd_wgrad_t.rows_y) keep their meaning when handed (m, r) and the zero coef written here.
+ *
+ * scd_bn_frozen_coeffs: mean, invstd, scale, shift [nseg][c], the same values for every segment (the layout the
+ * backward forms and the fused consumers read); the running statistics are read, never written. */
+int scd_bn_frozen_coeffs(int32_t c, int32_t nseg, const float *gamma, const float *beta, const float *running_mean,
+                         const float *running_var, float eps, float *mean, float *invstd, float *scale, float *shift,
+                         scd_stream_t stream);
+
+/* Every form of the BatchNorm + ReLU backward behind one descriptor.  Without SCD_BN_BWD_FROZEN a form is exactly its
+ * entry point above; with it, mean / invstd are scd_bn_frozen_coeffs' and the coefficients are zero (see above), in
+ * every form.  Fields a form does not use are ignored (zero them). */
+enum scd_bn_bwd_form {
+    SCD_BN_BWD_PLAIN = 0,   /* scd_bn_relu_backward:         da */
+    SCD_BN_BWD_TILES = 1,   /* scd_bn_relu_backward_tiles:   da, tile_rec, ntiles */
+    SCD_BN_BWD_POOLED = 2,  /* scd_bn_relu_backward_pooled:  gy, idx, gskip, skip_mode 0 / 1 */
+    SCD_BN_BWD_POOLED2 = 3, /* scd_bn_relu_backward_pooled2: ... and gskip2, skip_mode 2 */
+    SCD_BN_BWD_HEAD = 4,    /* scd_bn_relu_backward_head:    gout, w_head, n_out, w_grad (optional) */
+    SCD_BN_BWD_COEF = 5     /* scd_bn_relu_backward_coef:    da or tile_rec / ntiles, coef, da_bound; no dy */
+};
+#define SCD_BN_BWD_FROZEN 1u
+typedef struct scd_bn_bwd {
+    int32_t form; /* enum scd_bn_bwd_form */
+    uint32_t flags;
+    scd_nhwc_t y;
+    int32_t nseg;
+    const float *mean, *invstd, *gamma, *scale, *shift;
+    float *dgamma, *dbeta, *dbias_prev;
+    scd_nhwc_t dy;
+    float *dy_bound;
+    void *ws;
+    size_t ws_bytes;
+    scd_nhwc_t da;
+    const float *tile_rec;
+    int32_t ntiles;
+    scd_nhwc_t gy;
+    const uint8_t *idx;
+    scd_nhwc_t gskip;
+    int32_t skip_mode;
+    scd_nhwc_t gskip2;
+    const float *gout, *w_head;
+    int32_t n_out;
+    float *w_grad;
+    float *coef;
+    const float *da_bound;
+} scd_bn_bwd_t;
+int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream);
 
 /* out[c] = sum over all pixels of x[., c] (ConvTranspose2d bias grad, networks.py:433); workspace as
  * scd_bn_workspace_bytes(n, h, w, c, 1).  replaces: the bias-grad reduction of convolution_backward. */

@@ -294,6 +294,24 @@ __global__ void bn_eval_coeffs_kernel(int C, const float *gamma, const float *be
     shift[c] = float((beta ? beta[c] : 0.0f) - double(rm[c]) * sc);
 }
 
+// bn_eval_coeffs_kernel's scale/shift, and the running mean and invstd, once per segment: the [seg][C] layout the
+// backward walk reads (BnWalk.smean/sinv) for a BatchNorm that normalises with its running statistics.
+__global__ void bn_frozen_coeffs_kernel(int C, int nseg, const float *gamma, const float *beta, const float *rm,
+                                        const float *rv, float eps, float *mean, float *invstd, float *scale,
+                                        float *shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double inv = 1.0 / sqrt(double(rv[c]) + double(eps));
+    const float sc = float((gamma ? gamma[c] : 1.0f) * inv);
+    const float sh = float((beta ? beta[c] : 0.0f) - double(rm[c]) * sc);
+    for (int s = 0; s < nseg; ++s) {
+        mean[s * C + c] = rm[c];
+        invstd[s * C + c] = float(inv);
+        scale[s * C + c] = sc;
+        shift[s * C + c] = sh;
+    }
+}
+
 __device__ __forceinline__ float bn_relu(float y, float sc, float sh) { return fmaxf(fmaf(y, sc, sh), 0.f); }
 __device__ __forceinline__ f4 bn_relu4(f4 y, f4 sc, f4 sh) {
     return f4{bn_relu(y.x, sc.x, sh.x), bn_relu(y.y, sc.y, sh.y), bn_relu(y.z, sc.z, sh.z), bn_relu(y.w, sc.w, sh.w)};
@@ -921,11 +939,13 @@ __device__ __forceinline__ float bn_dy_bound(double da_bound, double n, double g
 // one workgroup per channel: coef[seg][C][2] = {mean(dz), mean(dz*xhat)}; dgamma/dbeta summed over segments.
 // dbias (optional; the deferred form, whose dy is formed by its consumer and never summed): sum(dy) from the sums,
 // sum_seg gamma*invstd * (S1 - pseg * k1) -- zero but for the rounding of k1, as BatchNorm removes the mean.
+// frozen (the BatchNorm normalises with its running statistics, smean/sinv hold those): the statistics do not depend
+// on y, so k1 = k2 = 0 -- dy = gamma*invstd*dz -- and the conv-bias sum above is the true gradient scale * dbeta.
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalize(const float *__restrict__ rec, int C, int nseg,
                                                               int ncps, int nrec, int64_t pseg, float *coef,
                                                               float *dgamma, float *dbeta, const float *gamma,
                                                               const float *sinv, float *dbias, const float *smean,
-                                                              const float *da_bound, float *dy_bound) {
+                                                              const float *da_bound, float *dy_bound, int frozen) {
     __shared__ double a1[BN_THREADS], a2[BN_THREADS];
     const int c = blockIdx.x;
     const int t = threadIdx.x;
@@ -968,8 +988,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalize(const float *__res
                 a1[0] += a1[k];
                 a2[0] += a2[k];
             }
-            const float k1 = float(a1[0] / double(pseg));
-            const float k2 = float(a2[0] / double(pseg));
+            const float k1 = frozen ? 0.f : float(a1[0] / double(pseg));
+            const float k2 = frozen ? 0.f : float(a2[0] / double(pseg));
             coef[(s * C + c) * 2 + 0] = k1;
             coef[(s * C + c) * 2 + 1] = k2;
             if (dy_bound) atomic_max_bound(dy_bound, bn_dy_bound(double(*da_bound), double(pseg), gamma ? gamma[c] : 1.0,
@@ -1243,6 +1263,19 @@ extern "C" int scd_bn_eval_coeffs(int32_t c, const float *gamma, const float *be
     return launch_status("scd_bn_eval_coeffs");
 }
 
+extern "C" int scd_bn_frozen_coeffs(int32_t c, int32_t nseg, const float *gamma, const float *beta,
+                                    const float *running_mean, const float *running_var, float eps, float *mean,
+                                    float *invstd, float *scale, float *shift, scd_stream_t stream) {
+    clear_error();
+    if (c < 1 || nseg < 1 || !running_mean || !running_var || !mean || !invstd || !scale || !shift) {
+        set_error("bn_frozen_coeffs: bad arguments");
+        return SCD_ERR_ARG;
+    }
+    hipLaunchKernelGGL(bn_frozen_coeffs_kernel, dim3((c + 127) / 128), dim3(128), 0, as_stream(stream), c, nseg, gamma,
+                       beta, running_mean, running_var, eps, mean, invstd, scale, shift);
+    return launch_status("scd_bn_frozen_coeffs");
+}
+
 extern "C" int scd_bn_relu_apply(scd_nhwc_t y, int32_t nseg, const float *scale, const float *shift, scd_nhwc_t a,
                                  scd_stream_t stream) {
     clear_error();
@@ -1281,6 +1314,9 @@ struct BnBwd {
     // coef[seg][c][2]
     BnGeom g;
     float *rec, *brec, *coef;
+    // save_mean / save_invstd are the running statistics of a BatchNorm that normalises with them (scd_bn_bwd_t,
+    // SCD_BN_BWD_FROZEN): bn_bwd_finalize then writes zero coefficients
+    bool frozen = false;
 
     // the kernels' parameter block for a walk over segments of lseg pixels (or cells) in ncps chunks of `chunk`
     BnWalk walk(int64_t lseg, int chunk, int ncps) const {
@@ -1351,7 +1387,7 @@ static void bn_bwd_run(const BnBwd &b, const BnWalk &w, BnRecs r, Partial partia
     if constexpr (!std::is_same_v<Partial, NoStep>) partial();
     hipLaunchKernelGGL(bn_bwd_finalize, dim3(b.y.c), dim3(BN_THREADS), 0, b.s, r.rec, b.y.c, b.nseg, r.ncps, r.nrec,
                        b.g.pseg, b.coef, b.dgamma, b.dbeta, b.gamma, b.save_invstd, deferred ? b.dbias_prev : nullptr,
-                       b.save_mean, da_bound, deferred ? b.dy_bound : nullptr);
+                       b.save_mean, da_bound, deferred ? b.dy_bound : nullptr, int(b.frozen));
     if constexpr (!deferred) {
         apply(b.dbias_prev ? b.brec : nullptr);
         if (b.dbias_prev)
@@ -1430,18 +1466,28 @@ static void bn_backward_run_pooled(const BnBwd &b, PooledCells<T> P) {
 }
 }  // namespace scd
 
-extern "C" int scd_bn_relu_backward(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                    const float *save_invstd, const float *gamma, const float *scale,
-                                    const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
-                                    scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
+// The entry points' bodies, shared with scd_bn_relu_backward_desc: `frozen` as BnBwd::frozen.
+static int bn_relu_backward_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                 const float *save_invstd, const float *gamma, const float *scale, const float *shift,
+                                 float *dgamma, float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
+                                 void *ws, size_t ws_bytes, scd_stream_t stream, bool frozen) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
+    b.frozen = frozen;
     SCD_TRY(bn_bwd_check("bn_relu_backward", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}}));
     const int dt = common_dtype("bn_relu_backward", {&y, &da, &dy});
     if (dt < 0) return SCD_ERR_ARG;
     SCD_WITH_T(dt, T, bn_backward_run<T>(b, DaPlain<T>{view_ptr<const T>(da), da.ldc}));
     return launch_status("scd_bn_relu_backward");
+}
+
+extern "C" int scd_bn_relu_backward(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                    const float *save_invstd, const float *gamma, const float *scale,
+                                    const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
+                                    scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    return bn_relu_backward_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev,
+                                 dy, dy_bound, ws, ws_bytes, stream, false);
 }
 
 extern "C" size_t scd_bn_head_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t nseg,
@@ -1452,14 +1498,15 @@ extern "C" size_t scd_bn_head_workspace_bytes(int32_t n, int32_t h, int32_t w, i
     return scd_bn_workspace_bytes(n, h, w, c, nseg) + size_t(n_out > 0 ? n_out : 1) * c * g.nrec * sizeof(float);
 }
 
-extern "C" int scd_bn_relu_backward_head(scd_nhwc_t y, const float *gout, const float *w_head, int32_t n_out,
-                                         int32_t nseg, const float *save_mean, const float *save_invstd,
-                                         const float *gamma, const float *scale, const float *shift, float *dgamma,
-                                         float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
-                                         float *w_grad, void *ws, size_t ws_bytes, scd_stream_t stream) {
+static int bn_relu_backward_head_impl(scd_nhwc_t y, const float *gout, const float *w_head, int32_t n_out,
+                                      int32_t nseg, const float *save_mean, const float *save_invstd,
+                                      const float *gamma, const float *scale, const float *shift, float *dgamma,
+                                      float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, float *w_grad,
+                                      void *ws, size_t ws_bytes, scd_stream_t stream, bool frozen) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
+    b.frozen = frozen;
     const size_t need = w_grad ? scd_bn_head_workspace_bytes(y.n, y.h, y.w, y.c, nseg, n_out) : 0;
     SCD_TRY(bn_bwd_check("bn_relu_backward_head", b, {{&dy, "bn_bwd_head.dy", false, true}}, need, [&] {
         if (gout && w_head && n_out >= 1 && n_out <= 4 && pixels(y) < (int64_t(1) << 31)) return SCD_OK;
@@ -1486,6 +1533,15 @@ extern "C" int scd_bn_relu_backward_head(scd_nhwc_t y, const float *gout, const 
     return launch_status("scd_bn_relu_backward_head");
 }
 
+extern "C" int scd_bn_relu_backward_head(scd_nhwc_t y, const float *gout, const float *w_head, int32_t n_out,
+                                         int32_t nseg, const float *save_mean, const float *save_invstd,
+                                         const float *gamma, const float *scale, const float *shift, float *dgamma,
+                                         float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
+                                         float *w_grad, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    return bn_relu_backward_head_impl(y, gout, w_head, n_out, nseg, save_mean, save_invstd, gamma, scale, shift,
+                                      dgamma, dbeta, dbias_prev, dy, dy_bound, w_grad, ws, ws_bytes, stream, false);
+}
+
 extern "C" int scd_bn_relu_backward_pooled(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
                                            int32_t skip_mode, int32_t nseg, const float *save_mean,
                                            const float *save_invstd, const float *gamma, const float *scale,
@@ -1500,15 +1556,16 @@ extern "C" int scd_bn_relu_backward_pooled(scd_nhwc_t y, scd_nhwc_t gy, const ui
                                         scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream);
 }
 
-extern "C" int scd_bn_relu_backward_pooled2(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
-                                            int32_t skip_mode, scd_nhwc_t gskip2, int32_t nseg,
-                                            const float *save_mean, const float *save_invstd, const float *gamma,
-                                            const float *scale, const float *shift, float *dgamma, float *dbeta,
-                                            float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
-                                            size_t ws_bytes, scd_stream_t stream) {
+static int bn_relu_backward_pooled_impl(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
+                                        int32_t skip_mode, scd_nhwc_t gskip2, int32_t nseg, const float *save_mean,
+                                        const float *save_invstd, const float *gamma, const float *scale,
+                                        const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
+                                        scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream,
+                                        bool frozen) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
+    b.frozen = frozen;
     const auto more = [&] {
         if ((!gy.data && !gskip.data) || pixels(y) >= (int64_t(1) << 31)) {
             set_error("bn_relu_backward_pooled: neither gy nor gskip / 2^31 pixels or more");
@@ -1567,14 +1624,26 @@ extern "C" int scd_bn_relu_backward_pooled2(scd_nhwc_t y, scd_nhwc_t gy, const u
     return launch_status("scd_bn_relu_backward_pooled");
 }
 
-extern "C" int scd_bn_relu_backward_tiles(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                          const float *save_invstd, const float *gamma, const float *scale,
-                                          const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
-                                          float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes,
-                                          scd_stream_t stream) {
+extern "C" int scd_bn_relu_backward_pooled2(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
+                                            int32_t skip_mode, scd_nhwc_t gskip2, int32_t nseg,
+                                            const float *save_mean, const float *save_invstd, const float *gamma,
+                                            const float *scale, const float *shift, float *dgamma, float *dbeta,
+                                            float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
+                                            size_t ws_bytes, scd_stream_t stream) {
+    return bn_relu_backward_pooled_impl(y, gy, idx, gskip, skip_mode, gskip2, nseg, save_mean, save_invstd, gamma,
+                                        scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream,
+                                        false);
+}
+
+static int bn_relu_backward_tiles_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                       const float *save_invstd, const float *gamma, const float *scale,
+                                       const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
+                                       float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
+                                       size_t ws_bytes, scd_stream_t stream, bool frozen) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
+    b.frozen = frozen;
     SCD_TRY(bn_bwd_check("bn_relu_backward_tiles", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}},
                          0, [&] {
                              if (tile_rec && ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)
@@ -1592,14 +1661,24 @@ extern "C" int scd_bn_relu_backward_tiles(scd_nhwc_t y, scd_nhwc_t da, int32_t n
     return launch_status("scd_bn_relu_backward_tiles");
 }
 
-extern "C" int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                         const float *save_invstd, const float *gamma, const float *scale,
-                                         const float *shift, const float *tile_rec, int32_t ntiles, float *coef,
-                                         float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
-                                         float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
+extern "C" int scd_bn_relu_backward_tiles(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                          const float *save_invstd, const float *gamma, const float *scale,
+                                          const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
+                                          float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes,
+                                          scd_stream_t stream) {
+    return bn_relu_backward_tiles_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, tile_rec, ntiles,
+                                       dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream, false);
+}
+
+static int bn_relu_backward_coef_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                      const float *save_invstd, const float *gamma, const float *scale,
+                                      const float *shift, const float *tile_rec, int32_t ntiles, float *coef,
+                                      float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
+                                      float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream, bool frozen) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, scd_nhwc_t{}, dy_bound, ws,
             ws_bytes, as_stream(stream)};
+    b.frozen = frozen;
     SCD_TRY(bn_bwd_check("bn_relu_backward_coef", b, {{&da, "bn_bwd_coef.da", tile_rec != nullptr, !tile_rec}}, 0, [&] {
         if (coef && (!tile_rec || (ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)) &&
             (!dy_bound || da_bound))
@@ -1620,6 +1699,58 @@ extern "C" int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t ns
                               NoStep{}, da_bound));
     }
     return launch_status("scd_bn_relu_backward_coef");
+}
+
+extern "C" int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                         const float *save_invstd, const float *gamma, const float *scale,
+                                         const float *shift, const float *tile_rec, int32_t ntiles, float *coef,
+                                         float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
+                                         float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    return bn_relu_backward_coef_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, tile_rec, ntiles, coef,
+                                      dgamma, dbeta, dbias_prev, da_bound, dy_bound, ws, ws_bytes, stream, false);
+}
+
+// Every form behind one descriptor (scd.h); the only way to the frozen mode.
+extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream) {
+    if (!d || (d->flags & ~uint32_t(SCD_BN_BWD_FROZEN))) {
+        clear_error();
+        set_error("bn_relu_backward_desc: null descriptor / unknown flags");
+        return SCD_ERR_ARG;
+    }
+    const bool frozen = (d->flags & SCD_BN_BWD_FROZEN) != 0;
+    switch (d->form) {
+        case SCD_BN_BWD_PLAIN:
+            return bn_relu_backward_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
+                                         d->dgamma, d->dbeta, d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes,
+                                         stream, frozen);
+        case SCD_BN_BWD_TILES:
+            return bn_relu_backward_tiles_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
+                                               d->tile_rec, d->ntiles, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
+                                               d->dy_bound, d->ws, d->ws_bytes, stream, frozen);
+        case SCD_BN_BWD_POOLED:
+        case SCD_BN_BWD_POOLED2:
+            if ((d->form == SCD_BN_BWD_POOLED2) != (d->skip_mode == 2)) {
+                clear_error();
+                set_error("bn_relu_backward_desc: skip_mode 2 is the form SCD_BN_BWD_POOLED2, and only it");
+                return SCD_ERR_ARG;
+            }
+            return bn_relu_backward_pooled_impl(d->y, d->gy, d->idx, d->gskip, d->skip_mode,
+                                                d->form == SCD_BN_BWD_POOLED2 ? d->gskip2 : scd_nhwc_t{}, d->nseg,
+                                                d->mean, d->invstd, d->gamma, d->scale, d->shift, d->dgamma, d->dbeta,
+                                                d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes, stream, frozen);
+        case SCD_BN_BWD_HEAD:
+            return bn_relu_backward_head_impl(d->y, d->gout, d->w_head, d->n_out, d->nseg, d->mean, d->invstd,
+                                              d->gamma, d->scale, d->shift, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
+                                              d->dy_bound, d->w_grad, d->ws, d->ws_bytes, stream, frozen);
+        case SCD_BN_BWD_COEF:
+            return bn_relu_backward_coef_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
+                                              d->tile_rec, d->ntiles, d->coef, d->dgamma, d->dbeta, d->dbias_prev,
+                                              d->da_bound, d->dy_bound, d->ws, d->ws_bytes, stream, frozen);
+        default:
+            clear_error();
+            set_error("bn_relu_backward_desc: unknown form %d", int(d->form));
+            return SCD_ERR_ARG;
+    }
 }
 
 extern "C" int scd_channel_sum(scd_nhwc_t x, float *out, void *ws, size_t ws_bytes, scd_stream_t stream) {

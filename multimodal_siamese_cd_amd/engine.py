@@ -359,11 +359,16 @@ def pad_in(c: int) -> int:
 # ------------------------------------------------------------------------------------------------
 @dataclass
 class _BNSaved:
+    """What a BatchNorm forward leaves for its backward.  frozen: the module normalised with its running statistics
+    (bn.training False); smean / sinv are then the running mean and 1/sqrt(running_var + eps), one set repeated per
+    segment, and the backward runs with zero coefficients (hip.bn_relu_backward*(frozen=True)).  smean None: a forward
+    that saved nothing for a backward (no gradient asked for)."""
     smean: torch.Tensor
     sinv: torch.Tensor
     scale: torch.Tensor
     shift: torch.Tensor
     nseg: int
+    frozen: bool = False
 
 
 # BatchNorm `num_batches_tracked` increments of one stage, applied in one foreach launch when the stage ends
@@ -409,8 +414,10 @@ def _bn_uses_batch_stats(bn: torch.nn.BatchNorm2d, training: bool) -> bool:
 
 
 def _bn_forward(y: torch.Tensor, bn: torch.nn.BatchNorm2d, nseg: int, training: bool, tiles=None,
-                bound=None) -> _BNSaved:
-    """Batch statistics (train) or running statistics (eval) -> per-segment scale/shift.
+                bound=None, save: bool = False) -> _BNSaved:
+    """Batch statistics (train) or running statistics (eval) -> per-segment scale/shift.  `training` is the
+    BatchNorm module's own flag; `save`: a backward may follow (eval mode then also leaves the running mean and invstd,
+    per segment, for it -- the frozen BatchNorm of fine-tuning; the running statistics are only read).
 
     `tiles` = (tile records, ntiles, pixels per tile) from the conv that produced y (fused statistics);
     without it the statistics are a separate pass over y.  `bound` (h2): a zeroed device float raised to a bound
@@ -435,6 +442,13 @@ def _bn_forward(y: torch.Tensor, bn: torch.nn.BatchNorm2d, nseg: int, training: 
         if update:
             _NBT_PENDING.append((bn.num_batches_tracked, nseg))
         return _traced(bn, y, _BNSaved(smean, sinv, scale, shift, nseg))
+    if save:
+        smean, sinv, scale, shift = (_empty((nseg * c,), y) for _ in range(4))
+        hip.bn_frozen_coeffs(c, nseg, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, smean, sinv, scale,
+                             shift)
+        if bound is not None:
+            hip.absmax_bound(nhwc(y), bound, nseg, scale, shift)
+        return _traced(bn, y, _BNSaved(smean, sinv, scale, shift, nseg, frozen=True))
     scale, shift = _empty((c,), y), _empty((c,), y)
     hip.bn_eval_coeffs(c, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, scale, shift)
     if bound is not None:
@@ -481,34 +495,39 @@ def _can_fuse_input_bn(y0: torch.Tensor, wpk1: torch.Tensor, y1: torch.Tensor, s
 
 
 def _dc_forward(x: torch.Tensor, dc, nseg: int, training: bool, save: bool, materialize: bool = True,
-                pool=None, x_bound=None):
+                pool=None, x_bound=None, bn_state: bool = False):
     """(a1, saved, y1, st1, b1); with materialize=False the output activation a1 = relu(BN1(y1)) is left to the
-    consumers (None is returned for it).  Under h2 (`pool` given) `x_bound` bounds x and b1 bounds a1."""
+    consumers (None is returned for it).  Under h2 (`pool` given) `x_bound` bounds x and b1 bounds a1.
+    Each BatchNorm follows its own `.training` flag, as in torch (a frozen BatchNorm inside a training model).
+    `training` -- here and in every run_* stage and _Meta that hands it down -- is the caller's model-level flag from
+    before that; it is vestigial, decides nothing, and stays only so that existing callers keep their signatures."""
     s = dc.conv
     conv0, bn0, conv1, bn1 = s[0], s[1], s[3], s[4]
+    train0, train1 = bn0.training, bn1.training
     cin = x.shape[3]
     if conv0.in_channels > cin:
         raise ValueError(f"DoubleConv expects {conv0.in_channels} input channels, got {cin}")
     if pool is not None and x_bound is None and (cin % 32 == 0 or cin == 16):
         x_bound = _bound_of(x, pool)  # the 16-channel input layer: the packing's bound (igemm_halo16_c16 h2)
     y0, t0 = _conv3x3_stats(x, packed_conv3x3(conv0.weight, 0, ci_pad=cin), conv0.bias,
-                            conv0.out_channels, _bn_uses_batch_stats(bn0, training), src_bound=x_bound)
+                            conv0.out_channels, _bn_uses_batch_stats(bn0, train0), src_bound=x_bound)
     b0 = _take(pool)
-    st0 = _bn_forward(y0, bn0, nseg, training, t0, b0)
+    st0 = _bn_forward(y0, bn0, nseg, train0, t0, b0, save)
+    # bn_state: BN1's statistics are kept for a backward outside this stage's own (the heads of run_heads)
     wpk1 = packed_conv3x3(conv1.weight, 0)
     n, h, w, _ = y0.shape
     y1 = _act((n, h, w, conv1.out_channels), y0)
     if _can_fuse_input_bn(y0, wpk1, y1, st0, save, b0):
         a0 = None  # never materialised: conv1 and its weight grad apply BN0 + ReLU while staging y0
-        y1, t1 = _conv3x3_stats(y0, wpk1, conv1.bias, conv1.out_channels, _bn_uses_batch_stats(bn1, training),
+        y1, t1 = _conv3x3_stats(y0, wpk1, conv1.bias, conv1.out_channels, _bn_uses_batch_stats(bn1, train1),
                                 in_bn=(st0.scale, st0.shift, st0.nseg), y=y1, src_bound=b0)
     else:
         a0 = torch.empty_like(y0)
         hip.bn_relu_apply(nhwc(y0), st0.nseg, st0.scale, st0.shift, nhwc(a0))
-        y1, t1 = _conv3x3_stats(a0, wpk1, conv1.bias, conv1.out_channels, _bn_uses_batch_stats(bn1, training), y=y1,
+        y1, t1 = _conv3x3_stats(a0, wpk1, conv1.bias, conv1.out_channels, _bn_uses_batch_stats(bn1, train1), y=y1,
                                 src_bound=b0)
     b1 = _take(pool)
-    st1 = _bn_forward(y1, bn1, nseg, training, t1, b1)
+    st1 = _bn_forward(y1, bn1, nseg, train1, t1, b1, save or bn_state)
     a1 = None
     if materialize:
         a1 = torch.empty_like(y1)
@@ -569,22 +588,22 @@ def _bn_backward(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, dy_bo
         if g.w_grad is not None:
             ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, g.n_out), y)
         hip.bn_relu_backward_head(nhwc(y), g.g, g.w2, g.n_out, st.nseg, st.smean, st.sinv, bn.weight, st.scale,
-                                  st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, g.w_grad)
+                                  st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, g.w_grad, frozen=st.frozen)
     elif isinstance(g, _PooledGrad) and g.gskip2 is not None:
         hip.bn_relu_backward_pooled2(nhwc(y), nhwc(g.gy) if g.gy is not None else hip._NULL, g.idx, nhwc(g.gskip),
                                      g.skip_mode, nhwc(g.gskip2), st.nseg, st.smean, st.sinv, bn.weight, st.scale,
-                                     st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound)
+                                     st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen)
     elif isinstance(g, _PooledGrad):
         hip.bn_relu_backward_pooled(nhwc(y), nhwc(g.gy) if g.gy is not None else hip._NULL, g.idx,
                                     nhwc(g.gskip) if g.gskip is not None else hip._NULL, g.skip_mode, st.nseg,
                                     st.smean, st.sinv, bn.weight, st.scale, st.shift, dgamma, dbeta, dbias, nhwc(dy),
-                                    ws, dy_bound)
+                                    ws, dy_bound, frozen=st.frozen)
     elif tiles is not None:
         hip.bn_relu_backward_tiles(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
-                                   tiles[0], tiles[1], dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound)
+                                   tiles[0], tiles[1], dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen)
     else:
         hip.bn_relu_backward(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift, dgamma,
-                             dbeta, dbias, nhwc(dy), ws, dy_bound)
+                             dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen)
     return dy, dgamma, dbeta, dbias
 
 
@@ -599,7 +618,7 @@ def _bn_backward_coef(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, 
     ws = _ws(hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
     hip.bn_relu_backward_coef(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
                               tiles[0] if tiles is not None else None, tiles[1] if tiles is not None else 0, coef,
-                              dgamma, dbeta, dbias, ws, da_bound, dy_bound)
+                              dgamma, dbeta, dbias, ws, da_bound, dy_bound, frozen=st.frozen)
     return dgamma, dbeta, dbias, coef
 
 
@@ -614,7 +633,7 @@ def _dgrad_bn_bwd(dy1: torch.Tensor, wpk: torch.Tensor, n_out: int, y0: torch.Te
     if pool is not None and hip.igemm_arith(nhwc(dy1), h, w, 1, TAPS_3X3, wpk, n_out, nhwc(ga0),
                                             src_bound=src_bound) == 'h2':
         gb = pool.take()
-    if _OPTS['fuse_bn_bwd'] and st0.smean is not None:
+    if _OPTS['fuse_bn_bwd']:
         ntiles, _ = hip.igemm_bn_bwd_tiles(nhwc(dy1), h, w, 1, TAPS_3X3, wpk, n_out, nhwc(ga0), src_bound)
         if ntiles and ntiles % st0.nseg == 0:
             rec = _empty((n_out * ntiles * 2,), dy1)
@@ -632,7 +651,7 @@ def _bn_backward_in_wgrad(y, g, st: _BNSaved, bn, conv, x, src_bn, x_bound, tile
     dbeta, dbias, weight grad, bound of dy) or None where the kernels do not take it (the caller then runs
     _bn_backward).  Under h2 the weight grad scales dy by a bound from the statistics (_bn_backward_coef, needs
     g_bound) and raises the exact max |dy| for the data grad."""
-    if not isinstance(g, torch.Tensor) or x.shape[3] > _OPTS['bn_bwd_in_wgrad'] or st.nseg > 2 or st.smean is None:
+    if not isinstance(g, torch.Tensor) or x.shape[3] > _OPTS['bn_bwd_in_wgrad'] or st.nseg > 2:
         return None
     if pool is not None and (g_bound is None or x_bound is None):
         return None
@@ -656,8 +675,6 @@ def _dc_backward(g_out, saved, dc, need_dx: bool, pool=None, dy1_given: bool = F
     x, y0, a0, st0, y1, st1, x_bound, b0 = saved
     s = dc.conv
     conv0, bn0, conv1, bn1 = s[0], s[1], s[3], s[4]
-    if st1.smean is None:
-        raise RuntimeError("backward through an eval-mode BatchNorm is not supported (call net.train())")
     src_bn1 = (st0.scale, st0.shift, st0.nseg) if a0 is None else None  # fused forward: y0 through BN0 + ReLU
     x1 = y0 if a0 is None else a0
     fused1 = None
@@ -677,7 +694,7 @@ def _dc_backward(g_out, saved, dc, need_dx: bool, pool=None, dy1_given: bool = F
         gw1 = _wgrad3x3(dy1, x1, conv1.weight, src_bn1, d1, b0)
     # the bound of ga0 (h2), only for a weight grad that forms BN0's dy itself: the input layer's (deferred) or one
     # _bn_backward_in_wgrad can take (its source width and segment count; it still checks the kernel's shape)
-    bwd_in_wgrad0 = need_dx and x.shape[3] <= _OPTS['bn_bwd_in_wgrad'] and st0.nseg <= 2 and st0.smean is not None
+    bwd_in_wgrad0 = need_dx and x.shape[3] <= _OPTS['bn_bwd_in_wgrad'] and st0.nseg <= 2
     ga0, tiles0, gb0 = _dgrad_bn_bwd(dy1, packed_conv3x3(conv1.weight, 1), conv1.in_channels, y0, st0, d1,
                                      pool if not need_dx or bwd_in_wgrad0 else None)
     if not need_dx and _OPTS['defer_bn_bwd'] and hip.wgrad_rows_bn_supported(nhwc(ga0), nhwc(x), 1, TAPS_3X3):
@@ -1146,7 +1163,8 @@ class DecoderFn(torch.autograd.Function):
                 hip.absmax_bound(nhwc(cat, cs, cto), cat_bound)
             last_raw = meta.raw and k == len(ups) - 1
             a, sv, y1, st1, _ = _dc_forward(cat, up.conv, meta.nseg, meta.training, meta.save,
-                                            materialize=not (last_into_head or last_raw), pool=pool, x_bound=cat_bound)
+                                            materialize=not (last_into_head or last_raw), pool=pool, x_bound=cat_bound,
+                                            bn_state=last_raw and meta.bn_state)
             saved.append((cur, cat, cs, sv, cur_bound))
             cur = a
             if last_raw:
@@ -1295,7 +1313,7 @@ def run_ups(ups: list, features: list, training: bool, cat_buffers: list | None 
             raise ValueError("run_decoder: the fused head expects OutConv's bias (networks.py:457)")
     save = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or any(f.requires_grad for f in features))
     meta = _Meta(ups=ups, training=training, save=save, cat_buffers=cat_buffers, head=head, raw=raw, nseg=nseg,
-                 raw_state=None)
+                 raw_state=None, bn_state=raw and torch.is_grad_enabled())
     try:
         out = DecoderFn.apply(meta, features[0], *features[1:1 + len(ups)], *params)
     finally:
@@ -1373,8 +1391,7 @@ class HeadsFn(torch.autograd.Function):
         dys, bn_grads, wgs = [], [], []
         for i, (y, src) in enumerate(zip(ys, meta.srcs)):
             st, dc = src.st, src.dc
-            if st.smean is None:
-                raise RuntimeError("backward through an eval-mode BatchNorm is not supported (call net.train())")
+            assert st.smean is not None  # run_ups(head='raw') keeps the statistics whenever a backward can follow
             bn, conv = dc.conv[4], dc.conv[3]
             n, h, w, c = y.shape
             ws_ = wall[:, offs[i]:offs[i] + cs[i]].contiguous()
@@ -1385,7 +1402,7 @@ class HeadsFn(torch.autograd.Function):
             db = _take(pool)
             ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, K), y)
             hip.bn_relu_backward_head(nhwc(y), g, ws_, K, st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
-                                      dgamma, dbeta, dbias, nhwc(dy), ws, db, wg)
+                                      dgamma, dbeta, dbias, nhwc(dy), ws, db, wg, frozen=st.frozen)
             dys.append(_set_bound(dy, db))
             bn_grads += [dgamma, dbeta, dbias]
             wgs.append(wg)

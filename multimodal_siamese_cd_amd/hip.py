@@ -37,6 +37,23 @@ class BNBWD(ctypes.Structure):
                 ("scale", c_void_p), ("shift", c_void_p), ("rec", c_void_p)]
 
 
+class BNBWDDESC(ctypes.Structure):
+    """scd_bn_bwd_t: every form of the BatchNorm + ReLU backward behind one descriptor (scd_bn_relu_backward_desc)."""
+
+    _fields_ = [("form", c_int32), ("flags", c_uint32), ("y", NHWC), ("nseg", c_int32), ("mean", c_void_p),
+                ("invstd", c_void_p), ("gamma", c_void_p), ("scale", c_void_p), ("shift", c_void_p),
+                ("dgamma", c_void_p), ("dbeta", c_void_p), ("dbias_prev", c_void_p), ("dy", NHWC),
+                ("dy_bound", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t), ("da", NHWC),
+                ("tile_rec", c_void_p), ("ntiles", c_int32), ("gy", NHWC), ("idx", c_void_p), ("gskip", NHWC),
+                ("skip_mode", c_int32), ("gskip2", NHWC), ("gout", c_void_p), ("w_head", c_void_p),
+                ("n_out", c_int32), ("w_grad", c_void_p), ("coef", c_void_p), ("da_bound", c_void_p)]
+
+
+# enum scd_bn_bwd_form, SCD_BN_BWD_FROZEN
+BN_BWD_PLAIN, BN_BWD_TILES, BN_BWD_POOLED, BN_BWD_POOLED2, BN_BWD_HEAD, BN_BWD_COEF = range(6)
+BN_BWD_FROZEN = 1
+
+
 class IGEMM(ctypes.Structure):
     _fields_ = [
         ("src", NHWC),
@@ -221,6 +238,9 @@ _SIGS = {
     "scd_threshold_counts_workspace_bytes": ([c_int64, c_int32], c_size_t),
     "scd_threshold_counts": (
         [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+    "scd_bn_frozen_coeffs": ([c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p], c_int),
+    "scd_bn_relu_backward_desc": ([POINTER(BNBWDDESC), c_void_p], c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -791,6 +811,31 @@ def bn_eval_coeffs(c, gamma, beta, rmean, rvar, eps, scale, shift):
                                     scale.data_ptr(), shift.data_ptr(), _stream()), "scd_bn_eval_coeffs")
 
 
+def bn_frozen_coeffs(c, nseg, gamma, beta, rmean, rvar, eps, mean, invstd, scale, shift):
+    """bn_eval_coeffs' scale/shift with the running mean and invstd, each [nseg][c] (one set, repeated per segment):
+    what the backward through a BatchNorm that uses its running statistics reads (bn_relu_backward*(frozen=True))."""
+    _check(lib().scd_bn_frozen_coeffs(c, nseg, _ptr(gamma), _ptr(beta), rmean.data_ptr(), rvar.data_ptr(), eps,
+                                      mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                      _stream()), "scd_bn_frozen_coeffs")
+
+
+def _bn_backward_frozen(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws,
+                        dy_bound, **fields):
+    """A backward form in frozen mode (scd_bn_relu_backward_desc, SCD_BN_BWD_FROZEN): smean / sinv are
+    bn_frozen_coeffs'.  `fields`: the form's own descriptor fields (NHWC views, pointers or ints)."""
+    d = BNBWDDESC()
+    d.form, d.flags, d.y, d.nseg = form, BN_BWD_FROZEN, y, nseg
+    d.mean, d.invstd, d.gamma, d.scale, d.shift = smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), \
+        shift.data_ptr()
+    d.dgamma, d.dbeta, d.dbias_prev = _ptr(dgamma), _ptr(dbeta), _ptr(dbias)
+    if dy is not None:
+        d.dy = dy
+    d.dy_bound, d.ws, d.ws_bytes = _ptr(dy_bound), ws.data_ptr(), ws.numel()
+    for k, v in fields.items():
+        setattr(d, k, v)
+    _check(lib().scd_bn_relu_backward_desc(ctypes.byref(d), _stream()), "scd_bn_relu_backward_desc")
+
+
 def absmax_bound(x: NHWC, bound: torch.Tensor, nseg: int = 1, scale=None, shift=None):
     """bound = max(bound, max |x|) (or of relu(x * scale + shift) per segment); bound is a device float."""
     _check(lib().scd_absmax_bound(x, nseg, _ptr(scale), _ptr(shift), bound.data_ptr(), _stream()), "scd_absmax_bound")
@@ -801,8 +846,12 @@ def bn_relu_apply(y: NHWC, nseg, scale, shift, a: NHWC):
 
 
 def bn_relu_backward(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws,
-                     dy_bound=None):
-    """`dy_bound`: device float raised to max |dy| (SCD_MATH_H2 operand scaling of the convs reading dy)."""
+                     dy_bound=None, frozen=False):
+    """`dy_bound`: device float raised to max |dy| (SCD_MATH_H2 operand scaling of the convs reading dy).
+    `frozen` (every backward form): the BatchNorm used its running statistics; smean / sinv are bn_frozen_coeffs'."""
+    if frozen:
+        return _bn_backward_frozen(BN_BWD_PLAIN, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+                                   ws, dy_bound, da=da)
     _check(
         lib().scd_bn_relu_backward(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
                                    shift.data_ptr(), _ptr(dgamma), _ptr(dbeta), _ptr(dbias), dy, _ptr(dy_bound),
@@ -811,8 +860,11 @@ def bn_relu_backward(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, 
 
 
 def bn_relu_backward_pooled(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int, nseg, smean, sinv, gamma, scale,
-                            shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None):
+                            shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, frozen=False):
     """bn_relu_backward of da = maxpool_bwd(gy, idx) -/+ gskip (feature_grad's operand, never materialised)."""
+    if frozen:
+        return _bn_backward_frozen(BN_BWD_POOLED, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+                                   ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode)
     _check(
         lib().scd_bn_relu_backward_pooled(y, gy, _ptr(idx), gskip, skip_mode, nseg, smean.data_ptr(), sinv.data_ptr(),
                                           _ptr(gamma), scale.data_ptr(), shift.data_ptr(), _ptr(dgamma), _ptr(dbeta),
@@ -821,9 +873,13 @@ def bn_relu_backward_pooled(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int,
 
 
 def bn_relu_backward_pooled2(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int, gskip2: NHWC, nseg, smean, sinv,
-                             gamma, scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None):
+                             gamma, scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, frozen=False):
     """bn_relu_backward_pooled with the dual-task second skip gradient (skip_mode 2: gskip2 = the semantic decoder's
     [t2; t1] skip gradient, added to the -/+ difference gradient before the pooled term)."""
+    if frozen:
+        return _bn_backward_frozen(BN_BWD_POOLED2, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias,
+                                   dy, ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode,
+                                   gskip2=gskip2)
     _check(
         lib().scd_bn_relu_backward_pooled2(y, gy, _ptr(idx), gskip, skip_mode, gskip2, nseg, smean.data_ptr(),
                                            sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), shift.data_ptr(),
@@ -837,10 +893,14 @@ def bn_head_workspace_bytes(n, h, w, c, nseg, n_out) -> int:
 
 
 def bn_relu_backward_head(y: NHWC, gout: torch.Tensor, w_head: torch.Tensor, n_out: int, nseg, smean, sinv, gamma,
-                          scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, w_grad=None):
+                          scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, w_grad=None, frozen=False):
     """bn_relu_backward of da = gout . w_head, the 1x1 head's input gradient (conv1x1_bwd's gx, never materialised);
     gout NCHW [n][n_out][h][w], w_head [n_out][C].  `w_grad` ([n_out][C]): also the head's weight grad from the same
     pass (workspace bn_head_workspace_bytes)."""
+    if frozen:
+        return _bn_backward_frozen(BN_BWD_HEAD, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+                                   ws, dy_bound, gout=gout.data_ptr(), w_head=w_head.data_ptr(), n_out=n_out,
+                                   w_grad=_ptr(w_grad))
     _check(
         lib().scd_bn_relu_backward_head(y, gout.data_ptr(), w_head.data_ptr(), n_out, nseg, smean.data_ptr(),
                                         sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), shift.data_ptr(), _ptr(dgamma),
@@ -850,8 +910,11 @@ def bn_relu_backward_head(y: NHWC, gout: torch.Tensor, w_head: torch.Tensor, n_o
 
 
 def bn_relu_backward_tiles(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, tile_rec, ntiles, dgamma, dbeta,
-                           dbias, dy: NHWC, ws, dy_bound=None):
+                           dbias, dy: NHWC, ws, dy_bound=None, frozen=False):
     """bn_relu_backward with the partial sums from conv-epilogue tile records (conv_igemm(..., bn_bwd=...))."""
+    if frozen:
+        return _bn_backward_frozen(BN_BWD_TILES, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+                                   ws, dy_bound, da=da, tile_rec=tile_rec.data_ptr(), ntiles=ntiles)
     _check(
         lib().scd_bn_relu_backward_tiles(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
                                          shift.data_ptr(), tile_rec.data_ptr(), ntiles, _ptr(dgamma), _ptr(dbeta),
@@ -860,11 +923,15 @@ def bn_relu_backward_tiles(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, s
 
 
 def bn_relu_backward_coef(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, tile_rec, ntiles, coef, dgamma,
-                          dbeta, dbias, ws, da_bound=None, dy_bound=None):
+                          dbeta, dbias, ws, da_bound=None, dy_bound=None, frozen=False):
     """The statistics half of bn_relu_backward(_tiles): coef [nseg][C][2], dgamma, dbeta, dbias (sum dy, from the
     sums) for a consumer that forms dy itself (wgrad_plan(..., rows_bn=...)).  tile_rec None: a pass over (y, da).
     `dy_bound` (with `da_bound`, a bound of |da|): raised to a bound of |dy| from the statistics (the h2 rows bound of
     that consumer)."""
+    if frozen:
+        return _bn_backward_frozen(BN_BWD_COEF, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, None,
+                                   ws, dy_bound, da=da, tile_rec=_ptr(tile_rec), ntiles=ntiles, coef=coef.data_ptr(),
+                                   da_bound=_ptr(da_bound))
     _check(
         lib().scd_bn_relu_backward_coef(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
                                         shift.data_ptr(), _ptr(tile_rec), ntiles, coef.data_ptr(), _ptr(dgamma),

@@ -29,7 +29,7 @@ def _evaluate(net, cfg, device, run_types, epoch_float, step, rank):
     module = net.module if isinstance(net, torch.nn.parallel.DistributedDataParallel) else net
     for rt in run_types:
         evaluation.model_evaluation(module, cfg, device, rt, epoch_float, step)
-    net.train()
+    networks.apply_freeze_bn(net.train(), cfg)
 
 
 def _checked_loss(value: float, cfg, step: int) -> float:
@@ -87,7 +87,7 @@ def run_training(cfg, device, max_steps: int | None = None):
         for _ in range(steps_per_epoch):
             batch = next(batches) if batches is not None else datasets.synthetic_batch(
                 cfg, int(cfg.TRAINER.BATCH_SIZE), device, gen)
-            net.train()
+            networks.apply_freeze_bn(net.train(), cfg)  # TRAINER.FREEZE_BN: net.train() unfreezes, so every step
             optimizer.zero_grad(set_to_none=True)
             out = net(batch['x_t1'], batch['x_t2'])
             loss = trainers.step_loss(cfg, out, batch, net)

@@ -135,6 +135,45 @@ def load_checkpoint(epoch, cfg, device, net_file: Path = None):
     return net, optimizer, checkpoint['step']
 
 
+def _unwrapped(net):
+    while isinstance(net, (ModelWrapper, nn.parallel.DistributedDataParallel)):
+        net = net.module
+    return net
+
+
+def freeze_batchnorm(net, prefixes=None):
+    """Put BatchNorm2d modules in eval mode -- they normalise with their running statistics and leave them as they
+    are, while their affine parameters and everything around them keep training (fine-tuning from a checkpoint on
+    small batches): all of them, or those whose qualified name in the model (`inc.conv.conv.1`, wrappers aside)
+    starts with one of `prefixes`.  `net.train()` undoes it, so a loop calls this after each `net.train()`.
+    Returns `net`."""
+    if isinstance(prefixes, str):
+        prefixes = [prefixes]
+    prefixes = None if prefixes is None else tuple(str(p) for p in prefixes)
+    for name, mod in _unwrapped(net).named_modules():
+        if isinstance(mod, nn.BatchNorm2d) and (prefixes is None or name.startswith(prefixes)):
+            mod.eval()
+    return net
+
+
+def freeze_bn_setting(cfg):
+    """TRAINER.FREEZE_BN (absent: False): False, True (every BatchNorm) or a list of name prefixes."""
+    v = cfg.TRAINER.get('FREEZE_BN', False)
+    if v is None or isinstance(v, bool):
+        return bool(v)
+    if isinstance(v, (list, tuple)) and v and all(isinstance(p, str) for p in v):
+        return [str(p) for p in v]
+    raise ValueError(f"TRAINER.FREEZE_BN must be True, False or a non-empty list of name prefixes, got {v!r}")
+
+
+def apply_freeze_bn(net, cfg):
+    """freeze_batchnorm as TRAINER.FREEZE_BN asks (nothing when it is False or absent).  Returns `net`."""
+    v = freeze_bn_setting(cfg)
+    if v is False:
+        return net
+    return freeze_batchnorm(net, None if v is True else v)
+
+
 def _band_counts(cfg):
     return len(cfg.DATALOADER.S1_BANDS), len(cfg.DATALOADER.S2_BANDS)
 
@@ -170,6 +209,11 @@ class _HipNet(nn.Module):
     def _twin_forward(self, x_t1, x_t2):
         tw, (maps, bufs) = self._twin_ready(x_t1.device)
         tw.train(self.training)
+        any_bn_training = False
+        for name, mod in self.named_modules():  # each BatchNorm follows its own flag (freeze_batchnorm)
+            if isinstance(mod, nn.BatchNorm2d):
+                tw.get_submodule(name).training = mod.training
+                any_bn_training |= mod.training
         for k, p in self.named_parameters():
             shape, m = maps[k]
             mod_name, _, attr = k.rpartition('.')
@@ -182,7 +226,7 @@ class _HipNet(nn.Module):
                 else:
                     tb.copy_(b)
         out = tw._forward(x_t1, x_t2)
-        if self.training:
+        if any_bn_training:  # a frozen BatchNorm's statistics come back as they went
             with torch.no_grad():
                 for k, b in self.named_buffers():
                     tb, m = bufs[k]
@@ -385,19 +429,19 @@ def _two_stream_heads(net, x1, x2, nseg: int, siamese: bool):
     heads are one launch over both decoders' last BatchNorm + ReLU (engine.run_heads); else materialised outputs, a cat
     and three head launches."""
     heads = [(net.outc_fusion, (0, 1)), (net.outc_stream1, (0,)), (net.outc_stream2, (1,))]
+    if not net.training:  # eval mode returns the fusion logits alone: the stream heads are not run (and, as in torch,
+        heads = heads[:1]  # take no gradient from a backward through it)
     fused = _fused_heads(net.cfg, [h for h, _ in heads])
     head = 'raw' if fused else None
     d1, _ = _stream(net.inc_stream1, net.encoder_stream1, net.decoder_stream1, x1, nseg, net.training, siamese, head)
     d2, _ = _stream(net.inc_stream2, net.encoder_stream2, net.decoder_stream2, x2, nseg, net.training, siamese, head)
     if fused:
-        out_fusion, out_stream1, out_stream2 = engine.run_heads([d1, d2], heads)
+        outs = engine.run_heads([d1, d2], heads)
     else:
-        out_stream1 = engine.run_head(net.outc_stream1, d1)
-        out_stream2 = engine.run_head(net.outc_stream2, d2)
-        out_fusion = engine.run_head(net.outc_fusion, engine.cat_channels(d1, d2))
-    if net.training:
-        return out_fusion, out_stream1, out_stream2
-    return out_fusion
+        outs = [engine.run_head(net.outc_fusion, engine.cat_channels(d1, d2))]
+        if net.training:
+            outs += [engine.run_head(net.outc_stream1, d1), engine.run_head(net.outc_stream2, d2)]
+    return tuple(outs) if net.training else outs[0]
 
 
 class WhateverNet(_HipNet):

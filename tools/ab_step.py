@@ -13,6 +13,7 @@ A variant is a comma list of knob=value with knobs:
   pool_diff  encoder difference + next-level pooling in one pass (engine.set_options(pool_diff=...))
   pooled_bn_bwd  encoder BN backward forms maxpool_bwd -/+ diff grad on the fly (engine.set_options(...))
   defer_bn_bwd  input layer's BN backward formed inside its weight grad (engine.set_options(defer_bn_bwd=...))
+  freeze_bn  1: every BatchNorm2d in eval mode (networks.freeze_batchnorm: running statistics, frozen backward)
   <engine option>=0|1  any other engine.set_options switch by name (e.g. fuse_head=0)
 Prints per-variant median / min ms per step over the rounds.
 """
@@ -37,6 +38,7 @@ def apply(variant: str, model, math0: str):
     """Every variant starts from the defaults: tune bits 0, engine options and the config's arithmetic."""
     hip.set_tune(0)
     model.conv_math = math0
+    model.train()  # (undoes freeze_bn)
     engine.set_options(**_DEFAULT_OPTS)
     for kv in filter(None, variant.split(',')):
         k, v = kv.split('=')
@@ -58,6 +60,9 @@ def apply(variant: str, model, math0: str):
             engine.set_options(pooled_bn_bwd=bool(int(v)))
         elif k == 'defer_bn_bwd':
             engine.set_options(defer_bn_bwd=bool(int(v)))
+        elif k == 'freeze_bn':
+            if int(v):
+                networks.freeze_batchnorm(model)
         elif k == 'fuse_enc':
             engine.set_options(fuse_siamese_encoder=bool(int(v)))
         elif k == 'bn_bwd_in_wgrad':  # widest weight-grad source (channels) that forms its BatchNorm backward
