@@ -160,7 +160,9 @@ enum scd_conv_math {
  *  11: scd_igemm_kernel (scd_igemm_kernel_t, enum scd_igemm_family): the kernel instance of a conv launch, a host
  *      query; nothing existing changes and no kernel does.
  *      Still 11 (symbols appended, nothing existing changes): scd_bn_frozen_coeffs and scd_bn_relu_backward_desc
- *      (scd_bn_bwd_t, SCD_BN_BWD_FROZEN), the backward through a BatchNorm that uses its running statistics. */
+ *      (scd_bn_bwd_t, SCD_BN_BWD_FROZEN), the backward through a BatchNorm that uses its running statistics.
+ *      Still 11 (symbols appended, nothing existing changes): scd_input_grad and scd_input_grad_supported
+ *      (scd_input_grad_t, scd_input_grad_dst_t), the data grad of the channel-padded first layer. */
 #define SCD_ABI_VERSION 11
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
@@ -790,6 +792,42 @@ int scd_window_label_sums(const float *const *labels, const int32_t *hw, const i
 int scd_augment_apply(const float *const *src, const int32_t *hw, int32_t batch, int32_t channels, int32_t crop,
                       const int32_t *params, const double *scale, const double *gamma, float *out,
                       scd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Input gradient: the data grad of the first layer's 3x3 conv, from its C0 output channels down to the 1..16 real
+ * input bands that scd_pack_nchw zero-padded to the MFMA granule, stored straight into the callers' NCHW fp32
+ * tensors (no NHWC intermediate, no unpack pass):
+ *   gx[n][j][y][x] = sum_{o < C0} sum_{ky, kx < 3} dy[n][y+1-ky][x+1-kx][o] * w[o][j][ky][kx]     (zero padding)
+ * dy: dL/d(conv0 output), fp32 or bf16 storage, dy.c = C0 a multiple of 8, any h, w >= 1.  w: the conv's weight as
+ * the module holds it, OIHW fp32 [C0][cin][3][3], cin <= 16, read directly (no pack pass).  Every product and sum is
+ * fp32 (one fma chain per output) for either storage type; nothing is rounded to bf16.  Offsets are 64-bit: views of
+ * 2 GiB and more run as one launch.
+ * Up to two destination records say where the result goes: images [n_begin, n_begin + n_count) of dy, conv input
+ * channels [w_c, w_c + c_count), to dst[(n - n_begin)][c_begin + (j - w_c)][y][x] of an NCHW tensor of dst_c channels
+ * and n_count images.  The Siamese packing (images [0, B) from x_t1, [B, 2B) from x_t2) is two image ranges; the
+ * early-fusion packing (channels [0, nb) from x_t1's bands, [nb, 2nb) from x_t2's) is two channel ranges.  A record
+ * with dst == NULL is skipped (at least one must be set); nothing outside the given slices is written.
+ * replaces: the data-grad half of aten::convolution_backward of InConv's first conv (networks.py:392) and the
+ * backward of the channel slicing / concat in front of it (networks.py:74,105-106,113-114,141-142).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct scd_input_grad_dst {
+    float *dst;
+    int32_t dst_c;
+    int32_t c_begin;
+    int32_t c_count;
+    int32_t w_c;
+    int32_t n_begin;
+    int32_t n_count;
+} scd_input_grad_dst_t;
+typedef struct scd_input_grad {
+    scd_nhwc_t dy;
+    const float *w; /* OIHW [dy.c][cin][3][3] */
+    int32_t cin;
+    scd_input_grad_dst_t dst[2];
+} scd_input_grad_t;
+int scd_input_grad(const scd_input_grad_t *d, scd_stream_t stream);
+/* 1 if scd_input_grad would launch for `d`, else 0 with the reason in scd_last_error().  Host only. */
+int scd_input_grad_supported(const scd_input_grad_t *d);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,8 @@ Each Function runs a whole stage of the reference's forward (utils/networks.py) 
 calls on NHWC fp32 device buffers, and its backward as the reverse sequence:
 
   pack_pair / pack_stream  input NCHW -> NHWC (+ channel padding)        train_supervised.py:68-69
+  PackFn                   the same for inputs that require grad; its   x_t1.requires_grad_() (plain torch there)
+                           backward hands out scd_input_grad's NCHW result
   EncoderLevelFn           one level of InConv + Encoder (Down x L)       networks.py:313-343, 405-426
   SiameseLevelFn           the same on the t1/t2 pair batch, + f_t2 - f_t1 networks.py:141-150
   SiameseDiffFn            f_t2 - f_t1                                     networks.py:147-150
@@ -653,6 +655,8 @@ def _bn_backward_in_wgrad(y, g, st: _BNSaved, bn, conv, x, src_bn, x_bound, tile
     g_bound) and raises the exact max |dy| for the data grad."""
     if not isinstance(g, torch.Tensor) or x.shape[3] > _OPTS['bn_bwd_in_wgrad'] or st.nseg > 2:
         return None
+    if x.shape[3] == 16:  # the 16-channel-source weight grad forms dy while staging but has no dY store
+        return None
     if pool is not None and (g_bound is None or x_bound is None):
         return None
     rb = pool.take() if pool is not None else None
@@ -694,7 +698,7 @@ def _dc_backward(g_out, saved, dc, need_dx: bool, pool=None, dy1_given: bool = F
         gw1 = _wgrad3x3(dy1, x1, conv1.weight, src_bn1, d1, b0)
     # the bound of ga0 (h2), only for a weight grad that forms BN0's dy itself: the input layer's (deferred) or one
     # _bn_backward_in_wgrad can take (its source width and segment count; it still checks the kernel's shape)
-    bwd_in_wgrad0 = need_dx and x.shape[3] <= _OPTS['bn_bwd_in_wgrad'] and st0.nseg <= 2
+    bwd_in_wgrad0 = need_dx and x.shape[3] != 16 and x.shape[3] <= _OPTS['bn_bwd_in_wgrad'] and st0.nseg <= 2
     ga0, tiles0, gb0 = _dgrad_bn_bwd(dy1, packed_conv3x3(conv1.weight, 1), conv1.in_channels, y0, st0, d1,
                                      pool if not need_dx or bwd_in_wgrad0 else None)
     if not need_dx and _OPTS['defer_bn_bwd'] and hip.wgrad_rows_bn_supported(nhwc(ga0), nhwc(x), 1, TAPS_3X3):
@@ -719,9 +723,11 @@ def _dc_backward(g_out, saved, dc, need_dx: bool, pool=None, dy1_given: bool = F
             x_bound = _bound_of(x, pool)
         gw0 = _wgrad3x3(dy0, x, conv0.weight, None, d0, x_bound)
     gx = None
-    if need_dx:
-        if x.shape[3] != conv0.in_channels:
-            raise RuntimeError("input-gradient through a channel-padded first layer is not supported")
+    sink = _INPUT_SINK.get(x) if need_dx else None
+    if need_dx and (x.shape[3] != conv0.in_channels or (sink is not None and conv0.in_channels <= 16)):
+        # the model's first layer: its real bands only, straight into the callers' NCHW gradients (scd_input_grad)
+        gx = _input_grad(dy0, conv0, x, sink)
+    elif need_dx:
         n, h, w, _ = dy0.shape
         gx = _act((n, h, w, conv0.in_channels), dy0)
         wd = packed_conv3x3(conv0.weight, 1)
@@ -759,8 +765,8 @@ def _input_bound(like: torch.Tensor):
 def pack_pair(x_t1: torch.Tensor, x_t2: torch.Tensor, c_begin: int = 0, c_count: int | None = None) -> torch.Tensor:
     """Siamese input: [2B, H, W, pad_in(C)] NHWC with t1 images first (one shared-encoder batch)."""
     _check_input_pair(x_t1, x_t2)
-    if x_t1.requires_grad or x_t2.requires_grad:
-        raise NotImplementedError("input gradients are not computed by the HIP path")
+    if _wants_input_grad(x_t1, x_t2):
+        return _pack_with_grad(pack_pair, x_t1, x_t2, c_begin, c_count)
     b, c, h, w = x_t1.shape
     c_count = c - c_begin if c_count is None else c_count
     out = torch.empty((2 * b, h, w, pad_in(c_count)), device=x_t1.device, dtype=_STORAGE.get())
@@ -773,8 +779,8 @@ def pack_pair(x_t1: torch.Tensor, x_t2: torch.Tensor, c_begin: int = 0, c_count:
 def pack_stream(x_t1: torch.Tensor, x_t2: torch.Tensor, c_begin: int = 0, c_count: int | None = None) -> torch.Tensor:
     """Early-fusion input cat((t1[bands], t2[bands]), dim=1) as [B, H, W, pad_in(2*nb)] NHWC."""
     _check_input_pair(x_t1, x_t2)
-    if x_t1.requires_grad or x_t2.requires_grad:
-        raise NotImplementedError("input gradients are not computed by the HIP path")
+    if _wants_input_grad(x_t1, x_t2):
+        return _pack_with_grad(pack_stream, x_t1, x_t2, c_begin, c_count)
     b, c, h, w = x_t1.shape
     c_count = c - c_begin if c_count is None else c_count
     cp = pad_in(2 * c_count)
@@ -784,6 +790,118 @@ def pack_stream(x_t1: torch.Tensor, x_t2: torch.Tensor, c_begin: int = 0, c_coun
     hip.pack_nchw(x_t1.float(), c_begin, c_count, out, 0, cp, bound=bound)  # t1 bands -> [0, nb), zero-pad to cp
     hip.pack_nchw(x_t2.float(), c_begin, c_count, out, c_count, c_count, bound=bound)  # t2 bands -> [nb, 2nb)
     return _set_bound(out, bound)
+
+
+# ------------------------------------------------------------------------------------------------
+# Input gradients (x_t1.requires_grad_(): saliency, FGSM / PGD, virtual-adversarial terms).  The packing becomes an
+# autograd Function whose output requires grad, so the first level's stage Function sees needs_input_grad[0] and its
+# _dc_backward runs the first layer's data grad.  That conv (scd_input_grad) writes the real bands straight into NCHW
+# tensors shaped like the callers' inputs: the packed tensor's _InputSink tells it which images (pack_pair) or
+# channels (pack_stream) belong to which input, and the packing's backward hands those tensors to autograd.  Nothing
+# NHWC is formed on the way and nothing is unpacked.  Models with two streams pack twice; each packing returns its own
+# band slice (zeros elsewhere) and autograd adds them.
+# ------------------------------------------------------------------------------------------------
+_INPUT_SINK = _IdentityMap()  # packed input tensor -> its _InputSink
+
+
+def _wants_input_grad(x_t1: torch.Tensor, x_t2: torch.Tensor) -> bool:
+    return torch.is_grad_enabled() and (x_t1.requires_grad or x_t2.requires_grad)
+
+
+class _InputSink:
+    """Where the input gradient of one packed batch goes: per input, None (no gradient wanted) or the slice of an
+    NCHW fp32 tensor of the input's shape."""
+
+    def __init__(self, stream: bool, shape, c_begin: int, c_count: int, needs):
+        self.stream, self.shape, self.c_begin, self.c_count, self.needs = stream, tuple(shape), c_begin, c_count, needs
+        self.grads = None
+
+    def records(self, like: torch.Tensor, cin: int) -> list:
+        """Allocate the gradients and describe them as scd_input_grad destination records."""
+        b, c = self.shape[:2]
+        if cin != (2 if self.stream else 1) * self.c_count:
+            raise RuntimeError(f"input gradient: the first layer reads {cin} channels, the packing holds "
+                               f"{(2 if self.stream else 1) * self.c_count}")
+        new = torch.empty if self.c_count == c else torch.zeros  # bands this stream does not read: zero gradient
+        self.grads = [new(self.shape, device=like.device, dtype=_F32) if need else None for need in self.needs]
+        if self.stream:
+            return [(g, self.c_begin, self.c_count, i * self.c_count, 0, b) for i, g in enumerate(self.grads)]
+        return [(g, self.c_begin, self.c_count, 0, i * b, b) for i, g in enumerate(self.grads)]
+
+    def take(self):
+        grads, self.grads = self.grads, None
+        return grads
+
+
+class PackFn(torch.autograd.Function):
+    """pack_pair / pack_stream of inputs that require grad.  Forward: the same two scd_pack_nchw launches.  Backward:
+    the gradients the first layer's data grad already wrote for this packing (_InputSink), in each input's dtype."""
+
+    @staticmethod
+    def forward(ctx, x_t1, x_t2, meta):
+        ctx.set_materialize_grads(False)
+        ctx.meta = meta
+        ctx.dtypes = (x_t1.dtype, x_t2.dtype)
+        return meta.pack(x_t1.detach(), x_t2.detach(), meta.c_begin, meta.c_count)
+
+    @staticmethod
+    def backward(ctx, g):
+        meta = ctx.meta
+        grads = meta.sink.take()
+        if grads is None and g is not None:
+            # a first layer wider than scd_input_grad's 16 channels (not channel-padded): its generic data grad
+            # returned the packed NHWC gradient
+            grads = _unpack_grad(g, meta.sink)
+        if grads is None:
+            return None, None, None
+        return tuple(None if t is None else t.to(dt) for t, dt in zip(grads, ctx.dtypes)) + (None,)
+
+
+def _unpack_grad(g: torch.Tensor, sink: _InputSink) -> list:
+    b, c = sink.shape[:2]
+    nb, lo = sink.c_count, sink.c_begin
+    out = []
+    for i, need in enumerate(sink.needs):
+        if not need:
+            out.append(None)
+            continue
+        part = g[..., i * nb:(i + 1) * nb] if sink.stream else g[i * b:(i + 1) * b, ..., :nb]
+        t = torch.zeros(sink.shape, device=g.device, dtype=_F32)
+        t[:, lo:lo + nb] = part.permute(0, 3, 1, 2)
+        out.append(t)
+    return out
+
+
+def _pack_with_grad(pack, x_t1: torch.Tensor, x_t2: torch.Tensor, c_begin: int, c_count: int | None) -> torch.Tensor:
+    c = x_t1.shape[1]
+    c_count = c - c_begin if c_count is None else c_count
+    sink = _InputSink(pack is pack_stream, x_t1.shape, c_begin, c_count, (x_t1.requires_grad, x_t2.requires_grad))
+    meta = _Meta(pack=pack, c_begin=c_begin, c_count=c_count, sink=sink)
+    out = PackFn.apply(x_t1, x_t2, meta)
+    _INPUT_SINK.setdefault(out, sink)
+    return out
+
+
+def _input_grad(dy0: torch.Tensor, conv0, x: torch.Tensor, sink: '_InputSink | None'):
+    """dL/dx of the first layer's conv from dy0 = dL/d(conv0 output) (scd_input_grad).  With a sink (a model's packed
+    input) the result lands in the sink's NCHW tensors and None is returned: the packing's backward picks it up.
+    Without one (a stand-alone InConv / DoubleConv on channel-padded bands) the NHWC gradient of x is returned, zero
+    in the padded channels."""
+    cin = conv0.in_channels
+    if cin > 16:
+        raise RuntimeError(f"input gradient through a channel-padded first layer of {cin} channels is not supported "
+                           "(scd_input_grad takes at most 16)")
+    wt = conv0.weight.detach().contiguous()
+    if sink is not None:
+        hip.input_grad(nhwc(dy0), wt, sink.records(dy0, cin))
+        return None
+    n, h, w, _ = dy0.shape
+    g = _empty((n, cin, h, w), dy0)
+    hip.input_grad(nhwc(dy0), wt, [(g, 0, cin, 0, 0, n)])
+    g = g.permute(0, 2, 3, 1)
+    if x.shape[3] > cin:
+        g = torch.nn.functional.pad(g, (0, x.shape[3] - cin))
+    return g.contiguous().to(x.dtype)
 
 
 # ------------------------------------------------------------------------------------------------

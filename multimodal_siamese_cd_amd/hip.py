@@ -49,6 +49,19 @@ class BNBWDDESC(ctypes.Structure):
                 ("n_out", c_int32), ("w_grad", c_void_p), ("coef", c_void_p), ("da_bound", c_void_p)]
 
 
+class INPUTGRADDST(ctypes.Structure):
+    """scd_input_grad_dst_t: one NCHW destination slice of scd_input_grad."""
+
+    _fields_ = [("dst", c_void_p), ("dst_c", c_int32), ("c_begin", c_int32), ("c_count", c_int32), ("w_c", c_int32),
+                ("n_begin", c_int32), ("n_count", c_int32)]
+
+
+class INPUTGRAD(ctypes.Structure):
+    """scd_input_grad_t: the first layer's data grad, stored straight into up to two NCHW fp32 slices."""
+
+    _fields_ = [("dy", NHWC), ("w", c_void_p), ("cin", c_int32), ("dst", INPUTGRADDST * 2)]
+
+
 # enum scd_bn_bwd_form, SCD_BN_BWD_FROZEN
 BN_BWD_PLAIN, BN_BWD_TILES, BN_BWD_POOLED, BN_BWD_POOLED2, BN_BWD_HEAD, BN_BWD_COEF = range(6)
 BN_BWD_FROZEN = 1
@@ -241,6 +254,8 @@ _SIGS = {
     "scd_bn_frozen_coeffs": ([c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p], c_int),
     "scd_bn_relu_backward_desc": ([POINTER(BNBWDDESC), c_void_p], c_int),
+    "scd_input_grad": ([POINTER(INPUTGRAD), c_void_p], c_int),
+    "scd_input_grad_supported": ([POINTER(INPUTGRAD)], c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -834,6 +849,38 @@ def _bn_backward_frozen(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shi
     for k, v in fields.items():
         setattr(d, k, v)
     _check(lib().scd_bn_relu_backward_desc(ctypes.byref(d), _stream()), "scd_bn_relu_backward_desc")
+
+
+def input_grad_desc(dy: NHWC, weight: torch.Tensor, records) -> INPUTGRAD:
+    """scd_input_grad_t for conv weight `weight` (OIHW fp32 [dy.c][cin][3][3]) and up to two destination records
+    (dst NCHW fp32 tensor or None, c_begin, c_count, w_c, n_begin, n_count)."""
+    if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() != 4 or \
+            tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] != dy.c:
+        raise ValueError(f"input_grad: expected a contiguous fp32 [{dy.c}][cin][3][3] weight, got "
+                         f"{tuple(weight.shape)} {weight.dtype}")
+    if not 1 <= len(records) <= 2:
+        raise ValueError("input_grad: one or two destination records")
+    d = INPUTGRAD()
+    d.dy, d.w, d.cin = dy, weight.data_ptr(), weight.shape[1]
+    d._owner = (dy, weight, [r[0] for r in records])
+    for i, (dst, c_begin, c_count, w_c, n_begin, n_count) in enumerate(records):
+        if dst is None:
+            continue
+        if dst.dtype != torch.float32 or not dst.is_contiguous() or dst.dim() != 4 or \
+                tuple(dst.shape) != (n_count, dst.shape[1], dy.h, dy.w):
+            raise ValueError(f"input_grad: destination {i} must be a contiguous fp32 ({n_count}, C, {dy.h}, {dy.w}) "
+                             f"tensor, got {tuple(dst.shape)} {dst.dtype}")
+        r = d.dst[i]
+        r.dst, r.dst_c, r.c_begin, r.c_count, r.w_c, r.n_begin, r.n_count = \
+            dst.data_ptr(), dst.shape[1], c_begin, c_count, w_c, n_begin, n_count
+    return d
+
+
+def input_grad(dy: NHWC, weight: torch.Tensor, records):
+    """The first layer's data grad, written straight into the NCHW destinations (scd_input_grad): for each record,
+    dst[n - n_begin, c_begin + j, y, x] = sum_{o, ky, kx} dy[n, y+1-ky, x+1-kx, o] * weight[o, w_c + j, ky, kx]."""
+    d = input_grad_desc(dy, weight, records)
+    _check(lib().scd_input_grad(ctypes.byref(d), _stream()), "scd_input_grad")
 
 
 def absmax_bound(x: NHWC, bound: torch.Tensor, nseg: int = 1, scale=None, shift=None):

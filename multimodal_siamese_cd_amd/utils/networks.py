@@ -561,7 +561,8 @@ class DoubleConv(nn.Module):
 
 def _block(dc: DoubleConv, x, maxpool: bool):
     """DoubleConv (networks.py:386-402), behind MaxPool2d(2) for Down (415-426), on the engine's block Function.  A
-    source whose channels are not a multiple of 8 is zero-padded (its input gradient is then not available)."""
+    source whose channels are not a multiple of 8 is zero-padded; its input gradient (at most 16 real channels) comes
+    from scd_input_grad and to_nhwc's pad slices the padded channels off again."""
     cin = x.shape[1]
     cp = engine.pad_in(cin) if cin % 8 else cin
     y = engine.run_block(dc, engine.to_nhwc(x, cp), dc.training, maxpool=maxpool)
