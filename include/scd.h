@@ -162,7 +162,9 @@ enum scd_conv_math {
  *      Still 11 (symbols appended, nothing existing changes): scd_bn_frozen_coeffs and scd_bn_relu_backward_desc
  *      (scd_bn_bwd_t, SCD_BN_BWD_FROZEN), the backward through a BatchNorm that uses its running statistics.
  *      Still 11 (symbols appended, nothing existing changes): scd_input_grad and scd_input_grad_supported
- *      (scd_input_grad_t, scd_input_grad_dst_t), the data grad of the channel-padded first layer. */
+ *      (scd_input_grad_t, scd_input_grad_dst_t), the data grad of the channel-padded first layer.
+ *      Still 11 (one symbol appended, nothing existing changes): scd_bn_relu_through, the reduction-free backward
+ *      through a frozen BatchNorm whose parameters have no gradient reader. */
 #define SCD_ABI_VERSION 11
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
@@ -584,6 +586,23 @@ typedef struct scd_bn_bwd {
     const float *da_bound;
 } scd_bn_bwd_t;
 int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream);
+
+/* The backward through a BatchNorm + ReLU on its running statistics when nothing it could reduce has a reader: gamma,
+ * beta and the bias of the conv in front are all frozen (requires_grad False).  Then
+ *   dz = g * [fma(y, scale, shift) > 0]     dy = (gamma*invstd) * dz
+ * with g the form's gradient source, and no statistic of the gradient is needed: ONE launch of the form's apply walk
+ * (same geometry, 16-byte accesses and storage types), no partial pass, no finalize, no bias sum.  The stored dy is
+ * bit for bit scd_bn_relu_backward_desc's with SCD_BN_BWD_FROZEN (whose coefficients are zero).
+ *   forms: SCD_BN_BWD_PLAIN, _POOLED, _POOLED2 (the Siamese pair walk included) and _HEAD; _TILES and _COEF are
+ *          refused (no records are read and no coefficients exist);
+ *   mean, invstd, scale, shift: scd_bn_frozen_coeffs' [nseg][c] arrays (mean is not read);
+ *   dgamma, dbeta, dbias_prev, w_grad, coef: must be NULL; ws may be NULL and ws_bytes is ignored; flags: 0 or
+ *          SCD_BN_BWD_FROZEN, the same meaning;
+ *   dy_bound (optional): raised to max |dy| as stored, as by the other forms.
+ * Every check runs on the host before the launch; an error reads "through: ...".
+ * replaces: the backward of networks.py:393-394,396-397 under eval-mode BatchNorm with frozen parameters, where
+ * autograd forms neither batch-norm statistic nor parameter gradient. */
+int scd_bn_relu_through(const scd_bn_bwd_t *d, scd_stream_t stream);
 
 /* out[c] = sum over all pixels of x[., c] (ConvTranspose2d bias grad, networks.py:433); workspace as
  * scd_bn_workspace_bytes(n, h, w, c, 1).  replaces: the bias-grad reduction of convolution_backward. */

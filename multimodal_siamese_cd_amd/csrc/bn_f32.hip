@@ -590,6 +590,22 @@ struct SegCoef : SegStat {
         return stored4(dst, bn_bwd_dy4(y, g, mu, iv, sc, sf, k1, k2, mul));
     }
 };
+// ... and the apply kernels' constants when the BatchNorm normalised with its running statistics and nothing in front
+// of it trains (scd_bn_relu_through): dy = mul * dz, what SegCoef::dy stores with k1 = k2 = 0 (mul formed as there), so
+// no coefficients, no mean and no xhat.
+struct SegThrough {
+    f4 sc, sf, mul;
+    __device__ __forceinline__ void load(int seg, int c, const BnWalk &w) {
+        const int o = seg * w.C + c;
+        sc = ld4(w.scale + o), sf = ld4(w.shift + o);
+        const f4 gm = w.gamma ? ld4(w.gamma + c) : f4{1.f, 1.f, 1.f, 1.f};
+        mul = gm * ld4(w.sinv + o);
+    }
+    template <class T>
+    __device__ __forceinline__ f4 dy(const T *dst, f4 y, f4 g) const {
+        return stored4(dst, mul * relu_mask(y, sc, sf, g));
+    }
+};
 
 // The block epilogue of the backward and channel-sum kernels.  Every thread holds N sums of its channel quad over its
 // lane's pixels; block_tree_sum adds the lanes in a fixed tree (off = npl/2 .. 1, partner tid + off*qpb) and leaves
@@ -716,7 +732,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_partial(const T *__r
 }
 
 // bn_bwd_apply over cells (see bn_bwd_pooled_partial); brec[c][chunk] (conv bias grad) and dy_bound optional.
-template <class T, bool S2>
+// SC: the segment constants and the dy they form, SegCoef or (scd_bn_relu_through) SegThrough.
+template <class T, bool S2, class SC = SegCoef>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply(const T *__restrict__ y, int ldy, PooledCells<T> P,
                                                                   T *__restrict__ dy, int lddy, BnWalk w,
                                                                   float *__restrict__ brec, float *dy_bound) {
@@ -727,7 +744,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply(const T *__res
     f4 acc = {0.f, 0.f, 0.f, 0.f};
     f4 amax = acc;
     if (c < w.C) {
-        SegCoef st;
+        SC st;
         st.load(ch.seg, c, w);
         for (int64_t cell = ch.beg + pl; cell < ch.end; cell += npl) {
             f4 g[4];
@@ -755,7 +772,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply(const T *__res
 
 // bn_bwd_pooled_apply for a Siamese pair (see bn_bwd_pooled_partial_pair): both segments' dy per cell, the conv-bias
 // records of chunk k of each segment, bit-identical.
-template <class T, bool S2>
+template <class T, bool S2, class SC = SegCoef>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply_pair(const T *__restrict__ y, int ldy,
                                                                        PooledCells<T> P, T *__restrict__ dy, int lddy,
                                                                        BnWalk w, float *__restrict__ brec,
@@ -768,7 +785,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_pooled_apply_pair(const T *
     f4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
     f4 amax = acc0;
     if (c < w.C) {
-        SegCoef s0, s1;
+        SC s0, s1;
         s0.load(0, c, w);
         s1.load(1, c, w);
         for (int64_t cell = ch.beg + pl; cell < ch.end; cell += npl) {
@@ -1011,7 +1028,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalize(const float *__res
 }
 
 // dy = gamma*invstd*(dz - k1 - xhat*k2); optional per-chunk sums of dy (conv bias grad), brec[c][chunk]
-template <class T, class DA>
+// SC = SegThrough (scd_bn_relu_through): dy = gamma*invstd*dz, the same walk without the coefficient loads.
+template <class T, class DA, class SC = SegCoef>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply(const T *__restrict__ y, int ldy, DA da,
                                                            T *__restrict__ dy, int lddy, BnWalk w,
                                                            float *__restrict__ brec, float *dy_bound) {
@@ -1023,7 +1041,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply(const T *__restrict__
     f4 amax = acc;  // max |dy| of this thread (dy_bound)
     da.bind(c);
     if (c < w.C) {
-        SegCoef st;
+        SC st;
         st.load(ch.seg, c, w);
         int64_t p = ch.beg + pl;
         for (; p + 3 * npl < ch.end; p += 4 * npl) {
@@ -1298,6 +1316,9 @@ extern "C" int scd_bn_relu_apply(scd_nhwc_t y, int32_t nseg, const float *scale,
 }
 
 namespace scd {
+// How an entry point's body runs (its `mode`): train, SCD_BN_BWD_FROZEN, or scd_bn_relu_through's single pass.
+enum { BN_TRAIN = 0, BN_FROZEN = 1, BN_THROUGH = 2 };
+
 // What every form of the BatchNorm + ReLU backward shares: the entry points' common arguments as they received them,
 // then what bn_bwd_check derives from them.
 struct BnBwd {
@@ -1317,6 +1338,9 @@ struct BnBwd {
     // save_mean / save_invstd are the running statistics of a BatchNorm that normalises with them (scd_bn_bwd_t,
     // SCD_BN_BWD_FROZEN): bn_bwd_finalize then writes zero coefficients
     bool frozen = false;
+    // scd_bn_relu_through: only the apply kernel runs, on SegThrough; no workspace, no records, no coefficients
+    bool through = false;
+    void mode(int m) { frozen = m == BN_FROZEN, through = m == BN_THROUGH; }
 
     // the kernels' parameter block for a walk over segments of lseg pixels (or cells) in ncps chunks of `chunk`
     BnWalk walk(int64_t lseg, int chunk, int ncps) const {
@@ -1347,12 +1371,16 @@ static int bn_bwd_check(const char *who, BnBwd &b, std::initializer_list<BnView>
         return SCD_ERR_ARG;
     }
     SCD_TRY(more());
+    b.g = bn_geom(y, b.nseg);
+    if (b.through) {
+        b.rec = b.brec = b.coef = nullptr;
+        return SCD_OK;
+    }
     if (!need) need = scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, b.nseg);
     if (!b.ws || b.ws_bytes < need) {
         set_error("%s: workspace %zu < %zu bytes", who, b.ws_bytes, need);
         return SCD_ERR_WORKSPACE;
     }
-    b.g = bn_geom(y, b.nseg);
     b.rec = static_cast<float *>(b.ws);
     b.brec = b.rec + size_t(b.g.nrec) * y.c * 2;
     b.coef = b.brec + size_t(b.g.nrec) * y.c;
@@ -1404,10 +1432,10 @@ static auto pixel_partial(const BnBwd &b, const BnWalk &w, DA da) {
                            w.sinv, w.scale, w.shift, b.rec);
     };
 }
-template <class T, class DA>
+template <class T, class SC = SegCoef, class DA>
 static auto pixel_apply(const BnBwd &b, const BnWalk &w, DA da) {
     return [b, w, da](float *brec) {
-        hipLaunchKernelGGL((bn_bwd_apply<T, DA>), dim3(w.nrec, b.g.cgroups), dim3(BN_THREADS), 0, b.s,
+        hipLaunchKernelGGL((bn_bwd_apply<T, DA, SC>), dim3(w.nrec, b.g.cgroups), dim3(BN_THREADS), 0, b.s,
                            view_ptr<const T>(b.y), b.y.ldc, da, view_ptr<T>(b.dy), b.dy.ldc, w, brec, b.dy_bound);
     };
 }
@@ -1415,6 +1443,7 @@ static auto pixel_apply(const BnBwd &b, const BnWalk &w, DA da) {
 template <class T, class DA>
 static void bn_backward_run(const BnBwd &b, DA da) {
     const BnWalk w = b.pixel_walk();
+    if (b.through) return pixel_apply<T, SegThrough>(b, w, da)(nullptr);
     bn_bwd_run(b, w, walk_recs(b, w), pixel_partial<T>(b, w, da), pixel_apply<T>(b, w, da));
 }
 
@@ -1454,6 +1483,12 @@ static void bn_backward_run_pooled(const BnBwd &b, PooledCells<T> P) {
     const auto partial = pair ? bn_bwd_pooled_partial_pair<T, S2> : bn_bwd_pooled_partial<T, S2>;
     const auto apply = pair ? bn_bwd_pooled_apply_pair<T, S2> : bn_bwd_pooled_apply<T, S2>;
     const dim3 grid(pair ? w.ncps : w.nrec, b.g.cgroups);
+    if (b.through) {
+        const auto through = pair ? bn_bwd_pooled_apply_pair<T, S2, SegThrough> : bn_bwd_pooled_apply<T, S2, SegThrough>;
+        hipLaunchKernelGGL(through, grid, dim3(BN_THREADS), 0, b.s, view_ptr<const T>(y), y.ldc, P, view_ptr<T>(b.dy),
+                           b.dy.ldc, w, static_cast<float *>(nullptr), b.dy_bound);
+        return;
+    }
     bn_bwd_run(b, w, walk_recs(b, w),
                [&] {
                    hipLaunchKernelGGL(partial, grid, dim3(BN_THREADS), 0, b.s, view_ptr<const T>(y), y.ldc, P, w,
@@ -1466,15 +1501,16 @@ static void bn_backward_run_pooled(const BnBwd &b, PooledCells<T> P) {
 }
 }  // namespace scd
 
-// The entry points' bodies, shared with scd_bn_relu_backward_desc: `frozen` as BnBwd::frozen.
+// The entry points' bodies, shared with scd_bn_relu_backward_desc and scd_bn_relu_through: `mode` is BN_TRAIN,
+// BN_FROZEN or BN_THROUGH (BnBwd::mode).
 static int bn_relu_backward_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
                                  const float *save_invstd, const float *gamma, const float *scale, const float *shift,
                                  float *dgamma, float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
-                                 void *ws, size_t ws_bytes, scd_stream_t stream, bool frozen) {
+                                 void *ws, size_t ws_bytes, scd_stream_t stream, int mode) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.frozen = frozen;
+    b.mode(mode);
     SCD_TRY(bn_bwd_check("bn_relu_backward", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}}));
     const int dt = common_dtype("bn_relu_backward", {&y, &da, &dy});
     if (dt < 0) return SCD_ERR_ARG;
@@ -1487,7 +1523,7 @@ extern "C" int scd_bn_relu_backward(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, c
                                     const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
                                     scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
     return bn_relu_backward_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev,
-                                 dy, dy_bound, ws, ws_bytes, stream, false);
+                                 dy, dy_bound, ws, ws_bytes, stream, BN_TRAIN);
 }
 
 extern "C" size_t scd_bn_head_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t nseg,
@@ -1502,11 +1538,11 @@ static int bn_relu_backward_head_impl(scd_nhwc_t y, const float *gout, const flo
                                       int32_t nseg, const float *save_mean, const float *save_invstd,
                                       const float *gamma, const float *scale, const float *shift, float *dgamma,
                                       float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, float *w_grad,
-                                      void *ws, size_t ws_bytes, scd_stream_t stream, bool frozen) {
+                                      void *ws, size_t ws_bytes, scd_stream_t stream, int mode) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.frozen = frozen;
+    b.mode(mode);
     const size_t need = w_grad ? scd_bn_head_workspace_bytes(y.n, y.h, y.w, y.c, nseg, n_out) : 0;
     SCD_TRY(bn_bwd_check("bn_relu_backward_head", b, {{&dy, "bn_bwd_head.dy", false, true}}, need, [&] {
         if (gout && w_head && n_out >= 1 && n_out <= 4 && pixels(y) < (int64_t(1) << 31)) return SCD_OK;
@@ -1539,7 +1575,7 @@ extern "C" int scd_bn_relu_backward_head(scd_nhwc_t y, const float *gout, const 
                                          float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
                                          float *w_grad, void *ws, size_t ws_bytes, scd_stream_t stream) {
     return bn_relu_backward_head_impl(y, gout, w_head, n_out, nseg, save_mean, save_invstd, gamma, scale, shift,
-                                      dgamma, dbeta, dbias_prev, dy, dy_bound, w_grad, ws, ws_bytes, stream, false);
+                                      dgamma, dbeta, dbias_prev, dy, dy_bound, w_grad, ws, ws_bytes, stream, BN_TRAIN);
 }
 
 extern "C" int scd_bn_relu_backward_pooled(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
@@ -1561,11 +1597,11 @@ static int bn_relu_backward_pooled_impl(scd_nhwc_t y, scd_nhwc_t gy, const uint8
                                         const float *save_invstd, const float *gamma, const float *scale,
                                         const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
                                         scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream,
-                                        bool frozen) {
+                                        int mode) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.frozen = frozen;
+    b.mode(mode);
     const auto more = [&] {
         if ((!gy.data && !gskip.data) || pixels(y) >= (int64_t(1) << 31)) {
             set_error("bn_relu_backward_pooled: neither gy nor gskip / 2^31 pixels or more");
@@ -1632,18 +1668,18 @@ extern "C" int scd_bn_relu_backward_pooled2(scd_nhwc_t y, scd_nhwc_t gy, const u
                                             size_t ws_bytes, scd_stream_t stream) {
     return bn_relu_backward_pooled_impl(y, gy, idx, gskip, skip_mode, gskip2, nseg, save_mean, save_invstd, gamma,
                                         scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream,
-                                        false);
+                                        BN_TRAIN);
 }
 
 static int bn_relu_backward_tiles_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
                                        const float *save_invstd, const float *gamma, const float *scale,
                                        const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
                                        float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
-                                       size_t ws_bytes, scd_stream_t stream, bool frozen) {
+                                       size_t ws_bytes, scd_stream_t stream, int mode) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.frozen = frozen;
+    b.mode(mode);
     SCD_TRY(bn_bwd_check("bn_relu_backward_tiles", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}},
                          0, [&] {
                              if (tile_rec && ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)
@@ -1667,18 +1703,18 @@ extern "C" int scd_bn_relu_backward_tiles(scd_nhwc_t y, scd_nhwc_t da, int32_t n
                                           float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes,
                                           scd_stream_t stream) {
     return bn_relu_backward_tiles_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, tile_rec, ntiles,
-                                       dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream, false);
+                                       dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream, BN_TRAIN);
 }
 
 static int bn_relu_backward_coef_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
                                       const float *save_invstd, const float *gamma, const float *scale,
                                       const float *shift, const float *tile_rec, int32_t ntiles, float *coef,
                                       float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
-                                      float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream, bool frozen) {
+                                      float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream, int mode) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, scd_nhwc_t{}, dy_bound, ws,
             ws_bytes, as_stream(stream)};
-    b.frozen = frozen;
+    b.mode(mode);
     SCD_TRY(bn_bwd_check("bn_relu_backward_coef", b, {{&da, "bn_bwd_coef.da", tile_rec != nullptr, !tile_rec}}, 0, [&] {
         if (coef && (!tile_rec || (ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)) &&
             (!dy_bound || da_bound))
@@ -1707,7 +1743,7 @@ extern "C" int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t ns
                                          float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
                                          float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
     return bn_relu_backward_coef_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, tile_rec, ntiles, coef,
-                                      dgamma, dbeta, dbias_prev, da_bound, dy_bound, ws, ws_bytes, stream, false);
+                                      dgamma, dbeta, dbias_prev, da_bound, dy_bound, ws, ws_bytes, stream, BN_TRAIN);
 }
 
 // Every form behind one descriptor (scd.h); the only way to the frozen mode.
@@ -1717,16 +1753,16 @@ extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t str
         set_error("bn_relu_backward_desc: null descriptor / unknown flags");
         return SCD_ERR_ARG;
     }
-    const bool frozen = (d->flags & SCD_BN_BWD_FROZEN) != 0;
+    const int mode = (d->flags & SCD_BN_BWD_FROZEN) ? BN_FROZEN : BN_TRAIN;
     switch (d->form) {
         case SCD_BN_BWD_PLAIN:
             return bn_relu_backward_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
                                          d->dgamma, d->dbeta, d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes,
-                                         stream, frozen);
+                                         stream, mode);
         case SCD_BN_BWD_TILES:
             return bn_relu_backward_tiles_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
                                                d->tile_rec, d->ntiles, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
-                                               d->dy_bound, d->ws, d->ws_bytes, stream, frozen);
+                                               d->dy_bound, d->ws, d->ws_bytes, stream, mode);
         case SCD_BN_BWD_POOLED:
         case SCD_BN_BWD_POOLED2:
             if ((d->form == SCD_BN_BWD_POOLED2) != (d->skip_mode == 2)) {
@@ -1737,20 +1773,66 @@ extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t str
             return bn_relu_backward_pooled_impl(d->y, d->gy, d->idx, d->gskip, d->skip_mode,
                                                 d->form == SCD_BN_BWD_POOLED2 ? d->gskip2 : scd_nhwc_t{}, d->nseg,
                                                 d->mean, d->invstd, d->gamma, d->scale, d->shift, d->dgamma, d->dbeta,
-                                                d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes, stream, frozen);
+                                                d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes, stream, mode);
         case SCD_BN_BWD_HEAD:
             return bn_relu_backward_head_impl(d->y, d->gout, d->w_head, d->n_out, d->nseg, d->mean, d->invstd,
                                               d->gamma, d->scale, d->shift, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
-                                              d->dy_bound, d->w_grad, d->ws, d->ws_bytes, stream, frozen);
+                                              d->dy_bound, d->w_grad, d->ws, d->ws_bytes, stream, mode);
         case SCD_BN_BWD_COEF:
             return bn_relu_backward_coef_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
                                               d->tile_rec, d->ntiles, d->coef, d->dgamma, d->dbeta, d->dbias_prev,
-                                              d->da_bound, d->dy_bound, d->ws, d->ws_bytes, stream, frozen);
+                                              d->da_bound, d->dy_bound, d->ws, d->ws_bytes, stream, mode);
         default:
             clear_error();
             set_error("bn_relu_backward_desc: unknown form %d", int(d->form));
             return SCD_ERR_ARG;
     }
+}
+
+// The backward through a frozen BatchNorm + ReLU with nothing to train in front of it: dy = gamma*invstd*dz in one
+// launch of the form's apply kernel on SegThrough; no partial pass, no bn_bwd_finalize, no sum_records.
+extern "C" int scd_bn_relu_through(const scd_bn_bwd_t *d, scd_stream_t stream) {
+    clear_error();
+    const auto refuse = [](const char *why) {
+        set_error("through: %s", why);
+        return SCD_ERR_ARG;
+    };
+    if (!d) return refuse("null descriptor");
+    if (d->flags & ~uint32_t(SCD_BN_BWD_FROZEN)) return refuse("unknown flags");
+    switch (d->form) {
+        case SCD_BN_BWD_PLAIN:
+        case SCD_BN_BWD_POOLED:
+        case SCD_BN_BWD_POOLED2:
+        case SCD_BN_BWD_HEAD: break;
+        case SCD_BN_BWD_TILES: return refuse("the form SCD_BN_BWD_TILES has no records to read here (SCD_BN_BWD_PLAIN)");
+        case SCD_BN_BWD_COEF: return refuse("the form SCD_BN_BWD_COEF forms no dy; there are no coefficients here");
+        default: set_error("through: unknown form %d", int(d->form)); return SCD_ERR_ARG;
+    }
+    if (d->dgamma || d->dbeta || d->dbias_prev || d->w_grad || d->coef)
+        return refuse("dgamma, dbeta, dbias_prev, w_grad and coef must be null (nothing is reduced: "
+                      "scd_bn_relu_backward_desc forms them)");
+    if (!d->y.data || !d->dy.data) return refuse("null y.data / dy.data");
+    const bool pooled = d->form == SCD_BN_BWD_POOLED || d->form == SCD_BN_BWD_POOLED2;
+    if (pooled && (d->form == SCD_BN_BWD_POOLED2) != (d->skip_mode == 2))
+        return refuse("skip_mode 2 is the form SCD_BN_BWD_POOLED2, and only it");
+    int rc;
+    if (d->form == SCD_BN_BWD_PLAIN)
+        rc = bn_relu_backward_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift, nullptr,
+                                   nullptr, nullptr, d->dy, d->dy_bound, nullptr, 0, stream, BN_THROUGH);
+    else if (d->form == SCD_BN_BWD_HEAD)
+        rc = bn_relu_backward_head_impl(d->y, d->gout, d->w_head, d->n_out, d->nseg, d->mean, d->invstd, d->gamma,
+                                        d->scale, d->shift, nullptr, nullptr, nullptr, d->dy, d->dy_bound, nullptr,
+                                        nullptr, 0, stream, BN_THROUGH);
+    else
+        rc = bn_relu_backward_pooled_impl(d->y, d->gy, d->idx, d->gskip, d->skip_mode,
+                                          d->form == SCD_BN_BWD_POOLED2 ? d->gskip2 : scd_nhwc_t{}, d->nseg, d->mean,
+                                          d->invstd, d->gamma, d->scale, d->shift, nullptr, nullptr, nullptr, d->dy,
+                                          d->dy_bound, nullptr, 0, stream, BN_THROUGH);
+    if (rc != SCD_OK) {  // the shared bodies name their own entry points
+        const std::string why = scd_last_error();
+        set_error("through: %s", why.c_str());
+    }
+    return rc;
 }
 
 extern "C" int scd_channel_sum(scd_nhwc_t x, float *out, void *ws, size_t ws_bytes, scd_stream_t stream) {

@@ -37,7 +37,8 @@ _F32 = torch.float32
 _OPTS = {'fuse_input_bn': True, 'fuse_bn_bwd': True, 'fuse_siamese_encoder': True, 'batch_pack': True,
          'pack_cache': True, 'pool_diff': True, 'pooled_bn_bwd': True, 'defer_bn_bwd': True, 'fuse_head': True,
          'convT_bias_in_wgrad': True, 'head_wgrad_in_bn_bwd': True, 'fuse_plain_encoder': True,
-         'fuse_dualtask': True, 'dt_sem_batched': True, 'fuse_heads': True, 'bn_bwd_in_wgrad': 128}
+         'fuse_dualtask': True, 'dt_sem_batched': True, 'fuse_heads': True, 'bn_bwd_in_wgrad': 128,
+         'skip_frozen_grads': True}
 # bn_bwd_in_wgrad: the widest weight-grad source (channels) whose conv's plain BatchNorm backward is formed inside the
 # weight grad (0 = never).  Wider sources are split over more 64-channel tiles that each read the rows again, and
 # reading y and da instead of dy there cost more than the apply pass saved.  Same-process A/B
@@ -85,6 +86,12 @@ def set_options(**kw) -> dict:
     one launch over both decoders' last BatchNorm + ReLU (no cat, no materialised decoder outputs).
     bn_bwd_in_wgrad (int, channels): a plain BatchNorm backward whose conv's weight-grad source has at most this many
     channels is formed inside that weight grad, which also stores dy for the data grad (ABI 8): no apply pass; 0 = off.
+    skip_frozen_grads: a stage's backward reads ctx.needs_input_grad per parameter and input: the gradient of a frozen
+    parameter (requires_grad False) is not formed (no weight grad, no reduction; its slot returns None), a frozen
+    BatchNorm whose gamma, beta and conv bias in front are all frozen runs the reduction-free scd_bn_relu_through, and
+    the walk stops where the last reader is.  False: every gradient is computed and autograd discards the unread ones
+    (the behaviour before the option; for A/B timing and the equivalence tests).  With every parameter trainable the two
+    are the same launches.
     Returns the previous options."""
     prev = dict(_OPTS)
     for k, v in kw.items():
@@ -576,13 +583,49 @@ class _HeadGrad:
     w_grad: torch.Tensor | None = None  # also the head's weight grad ([n_out][C]) from the same pass
 
 
-def _bn_backward(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, dy_bound=None):
+def _needs(ctx, lo: int, count: int) -> tuple:
+    """ctx.needs_input_grad[lo:lo + count]: which of a stage's inputs and parameters have a reader for their gradient
+    (engine option skip_frozen_grads; off: all of them, as before the option)."""
+    if not _OPTS['skip_frozen_grads']:
+        return (True,) * count
+    return tuple(ctx.needs_input_grad[lo:lo + count])
+
+
+def _bn_through(st: _BNSaved, need_gamma: bool, need_beta: bool, need_bias: bool) -> bool:
+    """Whether a BatchNorm's backward takes the reduction-free route (scd_bn_relu_through): it normalised with its
+    running statistics and neither gamma, beta nor the bias of the conv in front has a reader (a train-mode BatchNorm
+    needs the gradient's statistics for dy itself, whatever trains)."""
+    return st.frozen and not (need_gamma or need_beta or need_bias)
+
+
+def _bn_backward_through(y, g, st: _BNSaved, bn, dy_bound=None):
+    """dy = gamma*invstd * g*[relu'] in one launch, no reduction; g as _bn_backward's."""
+    dy = torch.empty_like(y)
+    args = (nhwc(y), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift, nhwc(dy), dy_bound)
+    if isinstance(g, _HeadGrad):
+        hip.bn_relu_through(hip.BN_BWD_HEAD, *args, gout=g.g.data_ptr(), w_head=g.w2.data_ptr(), n_out=g.n_out)
+    elif isinstance(g, _PooledGrad):
+        fields = dict(gy=nhwc(g.gy) if g.gy is not None else hip._NULL, idx=hip._ptr(g.idx),
+                      gskip=nhwc(g.gskip) if g.gskip is not None else hip._NULL, skip_mode=g.skip_mode)
+        if g.gskip2 is not None:
+            hip.bn_relu_through(hip.BN_BWD_POOLED2, *args, gskip2=nhwc(g.gskip2), **fields)
+        else:
+            hip.bn_relu_through(hip.BN_BWD_POOLED, *args, **fields)
+    else:
+        hip.bn_relu_through(hip.BN_BWD_PLAIN, *args, da=nhwc(g))
+    return dy
+
+
+def _bn_backward(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, dy_bound=None, need=(True, True)):
     """`tiles` = (records, ntiles) of the partial sums from the conv epilogue that produced g; g may be a
-    _PooledGrad.  `dy_bound` (h2): a zeroed device float raised to max |dy|."""
+    _PooledGrad.  `dy_bound` (h2): a zeroed device float raised to max |dy|.  `need` = (dgamma, dbeta) have a reader
+    (conv_bias_grad: the conv bias exists and has one); the others are not formed and come back as None."""
+    if _bn_through(st, need[0], need[1], conv_bias_grad) and not (isinstance(g, _HeadGrad) and g.w_grad is not None):
+        return _bn_backward_through(y, g, st, bn, dy_bound), None, None, None
     c = y.shape[3]
     dy = torch.empty_like(y)
-    dgamma = _empty((c,), y)
-    dbeta = _empty((c,), y)
+    dgamma = _empty((c,), y) if need[0] else None
+    dbeta = _empty((c,), y) if need[1] else None
     dbias = _empty((c,), y) if conv_bias_grad else None
     n, h, w, _ = y.shape
     ws = _ws(hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
@@ -609,11 +652,14 @@ def _bn_backward(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, dy_bo
     return dy, dgamma, dbeta, dbias
 
 
-def _bn_backward_coef(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, da_bound=None, dy_bound=None):
+def _bn_backward_coef(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, da_bound=None, dy_bound=None,
+                      need=(True, True)):
     """The statistics half of _bn_backward (hip.bn_relu_backward_coef): (dgamma, dbeta, dbias, coef).  `dy_bound`
-    (h2, with `da_bound` bounding g): a zeroed device float raised to a bound of the dy the consumer forms."""
+    (h2, with `da_bound` bounding g): a zeroed device float raised to a bound of the dy the consumer forms.  `need`
+    as _bn_backward's."""
     c = y.shape[3]
-    dgamma, dbeta = _empty((c,), y), _empty((c,), y)
+    dgamma = _empty((c,), y) if need[0] else None
+    dbeta = _empty((c,), y) if need[1] else None
     dbias = _empty((c,), y) if conv_bias_grad else None
     coef = _empty((st.nseg * c * 2,), y)
     n, h, w, _ = y.shape
@@ -625,17 +671,18 @@ def _bn_backward_coef(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, 
 
 
 def _dgrad_bn_bwd(dy1: torch.Tensor, wpk: torch.Tensor, n_out: int, y0: torch.Tensor, st0: _BNSaved,
-                  src_bound=None, pool=None):
+                  src_bound=None, pool=None, records: bool = True):
     """Data-grad conv producing dL/da0, with BN0's backward partial sums fused into its epilogue when the kernel
     offers them.  Returns (ga0, tiles or None, bound of ga0 or None).  `pool` (h2): the epilogue also raises a bound
-    of ga0 where the kernel runs h2 (for a consumer that forms BN0's dy itself, _bn_backward_coef)."""
+    of ga0 where the kernel runs h2 (for a consumer that forms BN0's dy itself, _bn_backward_coef).  records=False:
+    BN0's backward is the reduction-free one, which reads no sums, so the plain data grad runs."""
     n, h, w, _ = dy1.shape
     ga0 = _act((n, h, w, n_out), dy1)
     gb = None
     if pool is not None and hip.igemm_arith(nhwc(dy1), h, w, 1, TAPS_3X3, wpk, n_out, nhwc(ga0),
                                             src_bound=src_bound) == 'h2':
         gb = pool.take()
-    if _OPTS['fuse_bn_bwd']:
+    if _OPTS['fuse_bn_bwd'] and records:
         ntiles, _ = hip.igemm_bn_bwd_tiles(nhwc(dy1), h, w, 1, TAPS_3X3, wpk, n_out, nhwc(ga0), src_bound)
         if ntiles and ntiles % st0.nseg == 0:
             rec = _empty((n_out * ntiles * 2,), dy1)
@@ -647,12 +694,14 @@ def _dgrad_bn_bwd(dy1: torch.Tensor, wpk: torch.Tensor, n_out: int, y0: torch.Te
     return ga0, None, gb
 
 
-def _bn_backward_in_wgrad(y, g, st: _BNSaved, bn, conv, x, src_bn, x_bound, tiles, g_bound, pool):
+def _bn_backward_in_wgrad(y, g, st: _BNSaved, bn, conv, x, src_bn, x_bound, tiles, g_bound, pool,
+                          need=(True, True, True)):
     """A plain BatchNorm backward whose dy is read by this conv's weight grad and then its data grad: the weight grad
     forms dy while staging and stores it (scd_wgrad_t.rows_y / rows_out), so no apply pass runs.  Returns (dy, dgamma,
     dbeta, dbias, weight grad, bound of dy) or None where the kernels do not take it (the caller then runs
     _bn_backward).  Under h2 the weight grad scales dy by a bound from the statistics (_bn_backward_coef, needs
-    g_bound) and raises the exact max |dy| for the data grad."""
+    g_bound) and raises the exact max |dy| for the data grad.  `need` = (dgamma, dbeta, conv bias grad) have a reader;
+    the caller comes here only when the weight grad has one."""
     if not isinstance(g, torch.Tensor) or x.shape[3] > _OPTS['bn_bwd_in_wgrad'] or st.nseg > 2:
         return None
     if x.shape[3] == 16:  # the 16-channel-source weight grad forms dy while staging but has no dY store
@@ -662,7 +711,8 @@ def _bn_backward_in_wgrad(y, g, st: _BNSaved, bn, conv, x, src_bn, x_bound, tile
     rb = pool.take() if pool is not None else None
     if not hip.wgrad_rows_bn_supported(nhwc(g), nhwc(x), 1, TAPS_3X3, src_bn, rb, x_bound if rb is not None else None):
         return None
-    dg, db, dbias, coef = _bn_backward_coef(y, g, st, bn, conv.bias is not None, tiles, g_bound, rb)
+    dg, db, dbias, coef = _bn_backward_coef(y, g, st, bn, conv.bias is not None and need[2], tiles, g_bound, rb,
+                                            need[:2])
     dy = torch.empty_like(y)
     ob = pool.take() if pool is not None else None
     rows_bn = (nhwc(y), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift, coef)
@@ -670,58 +720,80 @@ def _bn_backward_in_wgrad(y, g, st: _BNSaved, bn, conv, x, src_bn, x_bound, tile
     return dy, dg, db, dbias, gw, ob
 
 
-def _dc_backward(g_out, saved, dc, need_dx: bool, pool=None, dy1_given: bool = False):
+def _dc_backward(g_out, saved, dc, need_dx: bool, pool=None, dy1_given: bool = False, need=None):
     """g_out: gradient of the block output (a tensor, or a _PooledGrad formed inside the BatchNorm backward).
     Returns (grad wrt DoubleConv input or None, [8 param grads in dc_params order]).  `pool` (h2): bounds of the
     two BatchNorm-backward outputs, the operands of the data-grad and weight-grad convs.
     dy1_given: g_out is already the gradient of the second conv's output y1 (its BatchNorm backward ran in the heads'
-    backward, HeadsFn); that BatchNorm's and conv bias's gradients are then None here."""
+    backward, HeadsFn); that BatchNorm's and conv bias's gradients are then None here.
+    need: per parameter (dc_params order), whether its gradient has a reader (_needs; None: all).  A gradient without
+    one is not formed and comes back as None: no weight grad, no reduction for a frozen BatchNorm whose gamma, beta and
+    conv bias are frozen (_bn_through), and the walk ends after the second conv when neither the input nor anything of
+    the first conv and BatchNorm has a reader."""
     x, y0, a0, st0, y1, st1, x_bound, b0 = saved
     s = dc.conv
     conv0, bn0, conv1, bn1 = s[0], s[1], s[3], s[4]
+    nw0, nb0, ng0, nbt0, nw1, nb1, ng1, nbt1 = need if need is not None else (True,) * 8
+    nb0, nb1 = nb0 and conv0.bias is not None, nb1 and conv1.bias is not None
+    lower = need_dx or nw0 or nb0 or ng0 or nbt0  # a reader of the second conv's data grad
+    # a fused head's weight grad comes out of this BatchNorm's backward pass (_HeadGrad.w_grad): a reader too
+    head_wgrad = isinstance(g_out, _HeadGrad) and g_out.w_grad is not None
+    if not (lower or nw1 or head_wgrad or (not dy1_given and (nb1 or ng1 or nbt1))):
+        return None, [None] * 8
     src_bn1 = (st0.scale, st0.shift, st0.nseg) if a0 is None else None  # fused forward: y0 through BN0 + ReLU
     x1 = y0 if a0 is None else a0
-    fused1 = None
+    fused1 = gw1 = None
     if dy1_given:
         dy1, dg1, db1, dbias1 = g_out, None, None, None
         d1 = _bound_of(dy1, pool)
     else:
-        fused1 = _bn_backward_in_wgrad(y1, g_out, st1, bn1, conv1, x1, src_bn1, b0, None,
-                                       _ACT_BOUND.get(g_out) if pool is not None and isinstance(g_out, torch.Tensor)
-                                       else None, pool)
+        if nw1 and not _bn_through(st1, ng1, nbt1, nb1):
+            fused1 = _bn_backward_in_wgrad(y1, g_out, st1, bn1, conv1, x1, src_bn1, b0, None,
+                                           _ACT_BOUND.get(g_out) if pool is not None and
+                                           isinstance(g_out, torch.Tensor) else None, pool, (ng1, nbt1, nb1))
         if fused1 is not None:
             dy1, dg1, db1, dbias1, gw1, d1 = fused1
         else:
             d1 = _take(pool)
-            dy1, dg1, db1, dbias1 = _bn_backward(y1, g_out, st1, bn1, conv1.bias is not None, dy_bound=d1)
-    if fused1 is None:
+            dy1, dg1, db1, dbias1 = _bn_backward(y1, g_out, st1, bn1, nb1, dy_bound=d1, need=(ng1, nbt1))
+    if fused1 is None and nw1:
         gw1 = _wgrad3x3(dy1, x1, conv1.weight, src_bn1, d1, b0)
+    if not lower:
+        return None, [None, None, None, None, gw1, dbias1, dg1, db1]
+    through0 = _bn_through(st0, ng0, nbt0, nb0)
+    coef0 = nw0 and not through0  # a weight grad that forms BN0's dy itself (from its coefficients) may run
     # the bound of ga0 (h2), only for a weight grad that forms BN0's dy itself: the input layer's (deferred) or one
     # _bn_backward_in_wgrad can take (its source width and segment count; it still checks the kernel's shape)
-    bwd_in_wgrad0 = need_dx and x.shape[3] != 16 and x.shape[3] <= _OPTS['bn_bwd_in_wgrad'] and st0.nseg <= 2
+    bwd_in_wgrad0 = coef0 and need_dx and x.shape[3] != 16 and x.shape[3] <= _OPTS['bn_bwd_in_wgrad'] and \
+        st0.nseg <= 2
     ga0, tiles0, gb0 = _dgrad_bn_bwd(dy1, packed_conv3x3(conv1.weight, 1), conv1.in_channels, y0, st0, d1,
-                                     pool if not need_dx or bwd_in_wgrad0 else None)
-    if not need_dx and _OPTS['defer_bn_bwd'] and hip.wgrad_rows_bn_supported(nhwc(ga0), nhwc(x), 1, TAPS_3X3):
+                                     pool if (coef0 and not need_dx) or bwd_in_wgrad0 else None,
+                                     records=not through0)
+    if coef0 and not need_dx and _OPTS['defer_bn_bwd'] and \
+            hip.wgrad_rows_bn_supported(nhwc(ga0), nhwc(x), 1, TAPS_3X3):
         # the input layer: dy0 has one reader, the weight grad, which forms it while staging; under h2 its bound
         # comes from the statistics and the bound of ga0 (the h2 input-layer weight grad)
         rb0 = _take(pool) if gb0 is not None and x_bound is not None else None
-        dg0, db0, dbias0, coef = _bn_backward_coef(y0, ga0, st0, bn0, conv0.bias is not None, tiles0,
-                                                   gb0 if rb0 is not None else None, rb0)
+        dg0, db0, dbias0, coef = _bn_backward_coef(y0, ga0, st0, bn0, nb0, tiles0, gb0 if rb0 is not None else None,
+                                                   rb0, (ng0, nbt0))
         rows_bn = (nhwc(y0), st0.nseg, st0.smean, st0.sinv, bn0.weight, st0.scale, st0.shift, coef)
         gw0 = _wgrad3x3(ga0, x, conv0.weight, None, rb0, x_bound, rows_bn)
         return None, [gw0, dbias0, dg0, db0, gw1, dbias1, dg1, db1]
-    fused0 = _bn_backward_in_wgrad(y0, ga0, st0, bn0, conv0, x, None, x_bound, tiles0, gb0, pool) if need_dx else None
+    fused0 = _bn_backward_in_wgrad(y0, ga0, st0, bn0, conv0, x, None, x_bound, tiles0, gb0, pool,
+                                   (ng0, nbt0, nb0)) if need_dx and coef0 else None
     if fused0 is not None:
         dy0, dg0, db0, dbias0, gw0, d0 = fused0
     else:
         d0 = _take(pool)
-        dy0, dg0, db0, dbias0 = _bn_backward(y0, ga0, st0, bn0, conv0.bias is not None, tiles0, d0)
-        if pool is not None and x_bound is None and \
-                hip.wgrad_arith(hip.wgrad_desc(nhwc(dy0), nhwc(x), 1, TAPS_3X3, None, d0, d0)) == 'h2':
-            # a source the forward left unbounded (the channel-padded input layer, whose forward kernel is x3):
-            # bounded here, where that puts its weight grad (the generic kernel) on h2
-            x_bound = _bound_of(x, pool)
-        gw0 = _wgrad3x3(dy0, x, conv0.weight, None, d0, x_bound)
+        dy0, dg0, db0, dbias0 = _bn_backward(y0, ga0, st0, bn0, nb0, tiles0, d0, need=(ng0, nbt0))
+        gw0 = None
+        if nw0:
+            if pool is not None and x_bound is None and \
+                    hip.wgrad_arith(hip.wgrad_desc(nhwc(dy0), nhwc(x), 1, TAPS_3X3, None, d0, d0)) == 'h2':
+                # a source the forward left unbounded (the channel-padded input layer, whose forward kernel is x3):
+                # bounded here, where that puts its weight grad (the generic kernel) on h2
+                x_bound = _bound_of(x, pool)
+            gw0 = _wgrad3x3(dy0, x, conv0.weight, None, d0, x_bound)
     gx = None
     sink = _INPUT_SINK.get(x) if need_dx else None
     if need_dx and (x.shape[3] != conv0.in_channels or (sink is not None and conv0.in_channels <= 16)):
@@ -994,7 +1066,8 @@ class EncoderLevelFn(torch.autograd.Function):
         with hip.conv_scope(*meta.scope):
             sv, idx = ctx.saved
             ga = _level_grad(g_next, idx, g_a, 0, sv[4])
-            gx, pg = _dc_backward(ga, sv, meta.dc, need_dx=ctx.needs_input_grad[0], pool=_bounds(sv[4]))
+            gx, pg = _dc_backward(ga, sv, meta.dc, need_dx=ctx.needs_input_grad[0], pool=_bounds(sv[4]),
+                                  need=_needs(ctx, 2, 8))
         ctx.saved = None
         return (gx, None, *pg)
 
@@ -1087,7 +1160,8 @@ class DualTaskLevelFn(torch.autograd.Function):
                 if g_d is None:
                     g_d = torch.zeros((b,) + tuple(y1.shape[1:]), device=y1.device, dtype=y1.dtype)
                 ga = _PooledGrad(g_next, idx if g_next is not None else None, g_d, 2, g_o)
-            gx, pg = _dc_backward(ga, sv, meta.dc, need_dx=ctx.needs_input_grad[0], pool=_bounds(y1))
+            gx, pg = _dc_backward(ga, sv, meta.dc, need_dx=ctx.needs_input_grad[0], pool=_bounds(y1),
+                                  need=_needs(ctx, 2, 8))
         ctx.saved = None
         return (gx, None, *pg)
 
@@ -1168,7 +1242,8 @@ class SiameseLevelFn(torch.autograd.Function):
         with hip.conv_scope(*meta.scope):
             sv, idx = ctx.saved
             ga = _level_grad(g_next, idx, g_d, 1, sv[4])
-            gx, pg = _dc_backward(ga, sv, meta.dc, need_dx=ctx.needs_input_grad[0], pool=_bounds(sv[4]))
+            gx, pg = _dc_backward(ga, sv, meta.dc, need_dx=ctx.needs_input_grad[0], pool=_bounds(sv[4]),
+                                  need=_needs(ctx, 2, 8))
         ctx.saved = None
         return (gx, None, *pg)
 
@@ -1324,24 +1399,46 @@ class DecoderFn(torch.autograd.Function):
         if meta.head is None:
             g = g.contiguous()  # e.g. the gradient of a permuted (NCHW) view of the output, from a standalone Up
         pool = _bounds(g)
+        # readers (ctx.needs_input_grad: meta, x_deep, the skips, 10 parameters per Up, the fused head's two)
+        need_deep, need_skip = _needs(ctx, 1, 1)[0], _needs(ctx, 2, n)
+        need_p = [_needs(ctx, 2 + n + 10 * k, 10) for k in range(n)]
+        # below[k]: the gradient of Up k's input (x_deep, or the output of Up k - 1) has a reader
+        below = [need_deep] * n
+        for k in range(1, n):
+            below[k] = below[k - 1] or need_skip[k - 1] or any(need_p[k - 1])
         if meta.head is not None:
             y1, st1, w2, n_out, wshape, has_bias = ctx.head
+            need_hw, need_hb = _needs(ctx, 2 + 11 * n, 2)
+            need_hb = need_hb and has_bias
             g = g.contiguous()
-            gw = _empty(tuple(wshape), y1)
-            gb = _empty((n_out,), y1) if has_bias else None
-            ws = _ws(hip.conv1x1_workspace_bytes(nhwc(y1), n_out), y1)
+            gw = _empty(tuple(wshape), y1) if need_hw else None
+            gb = _empty((n_out,), y1) if need_hb else None
             # the head's weight grad comes from its BatchNorm's backward pass over y1 (scd_bn_relu_backward_head
             # w_grad); here only its bias grad
             fold = _OPTS['head_wgrad_in_bn_bwd']
-            hip.conv1x1_bwd_bn(nhwc(y1), st1.scale, st1.shift, st1.nseg, w2, g, n_out, None if fold else gw, gb, ws)
+            if need_hb or (need_hw and not fold):
+                ws = _ws(hip.conv1x1_workspace_bytes(nhwc(y1), n_out), y1)
+                hip.conv1x1_bwd_bn(nhwc(y1), st1.scale, st1.shift, st1.nseg, w2, g, n_out, None if fold else gw, gb,
+                                   ws)
             head_grads = [gw, gb]
             g = _HeadGrad(g, w2, n_out, gw if fold else None)
             ctx.head = None
+        g_deep = None
         for k in range(n - 1, -1, -1):
             up = ups[k]
             cur, cat, cs, sv, cur_bound = saved[k]
-            g_cat, pg = _dc_backward(g, sv, up.conv, need_dx=True, pool=pool, dy1_given=meta.raw and k == n - 1)
-            g_skips[k] = g_cat[..., :cs]
+            need_wT, need_bT = need_p[k][:2]
+            need_up = below[k] or need_wT or need_bT  # a reader of the ConvT half of the concat's gradient
+            head_wgrad = isinstance(g, _HeadGrad) and g.w_grad is not None  # formed by the last BatchNorm's backward
+            if not (need_up or need_skip[k] or any(need_p[k][2:]) or head_wgrad):
+                break  # nothing of this Up or below it takes a gradient
+            g_cat, pg = _dc_backward(g, sv, up.conv, need_dx=need_up or need_skip[k], pool=pool,
+                                     dy1_given=meta.raw and k == n - 1, need=need_p[k][2:])
+            if need_skip[k]:
+                g_skips[k] = g_cat[..., :cs]
+            grads[10 * k + 2:10 * k + 10] = pg
+            if not need_up:
+                break
             convT = up.up
             cto = convT.out_channels
             b, hc, wc, cu = cur.shape
@@ -1353,40 +1450,46 @@ class DecoderFn(torch.autograd.Function):
                 hh, ww = 2 * hc, 2 * wc
             else:
                 g_up = nhwc(g_cat, cs, cto)
-            # ConvT data grad: 4-tap stride-2 gather of g_cat's up half (h2: through g_cat's bound, raised by the
-            # DoubleConv data grad that wrote it)
-            g_cur = torch.empty_like(cur)
             gcat_bound = _bound_of(g_cat, pool)
-            # h2: the kernel raises g_cur's bound as it stores (a BatchNorm backward formed inside the next weight
-            # grad scales its dy by a bound derived from it, _bn_backward_in_wgrad)
-            wT = packed_convT2x2(convT.weight, 1)
-            gcur_bound = None
-            if pool is not None and _OPTS['bn_bwd_in_wgrad'] and k > 0 and \
-                    hip.igemm_arith(g_up, hc, wc, 2, TAPS_2X2, wT, cu, nhwc(g_cur), src_bound=gcat_bound) == 'h2':
-                gcur_bound = pool.take()
-            hip.conv_igemm(g_up, hc, wc, 2, TAPS_2X2, wT, cu, None, nhwc(g_cur), src_bound=gcat_bound,
-                           dst_bound=gcur_bound)
-            _set_bound(g_cur, gcur_bound)
-            # ConvT weight grad: rows = convT input, src = g_up gathered with stride 2 (h2: both bounds)
-            # (and its bias grad: the kernel sums the g_up columns it stages, scd_wgrad_t.src_colsum)
-            d, nsplit, nbytes = hip.wgrad_plan(nhwc(cur), g_up, 2, TAPS_2X2, None, cur_bound, gcat_bound)
-            slabs = _empty((nbytes // 4,), cur)
-            colsum = None
-            if _OPTS['convT_bias_in_wgrad'] and hip.wgrad_colsum_supported(d):
-                colsum = _empty((nsplit * 4 * cto,), cur)
-                d.src_colsum = colsum.data_ptr()
-            hip.conv_wgrad(d, slabs)
-            gwT = torch.empty_like(convT.weight)
-            hip.wgrad_finalize(slabs, nsplit, cu, 4, cto, 1, cto, gwT)
-            gbT = _empty((cto,), cur)
-            if colsum is not None:
-                hip.wgrad_colsum_finalize(colsum, nsplit, 4, cto, gbT)
-            else:
-                hip.channel_sum(g_up, gbT, _ws(hip.bn_workspace_bytes(bb, hh, ww, cto, 1), cur))
-            grads[10 * k:10 * k + 10] = [gwT, gbT] + pg
+            g_cur = None
+            if below[k]:
+                # ConvT data grad: 4-tap stride-2 gather of g_cat's up half (h2: through g_cat's bound, raised by the
+                # DoubleConv data grad that wrote it)
+                g_cur = torch.empty_like(cur)
+                # h2: the kernel raises g_cur's bound as it stores (a BatchNorm backward formed inside the next weight
+                # grad scales its dy by a bound derived from it, _bn_backward_in_wgrad)
+                wT = packed_convT2x2(convT.weight, 1)
+                gcur_bound = None
+                if pool is not None and _OPTS['bn_bwd_in_wgrad'] and k > 0 and \
+                        hip.igemm_arith(g_up, hc, wc, 2, TAPS_2X2, wT, cu, nhwc(g_cur), src_bound=gcat_bound) == 'h2':
+                    gcur_bound = pool.take()
+                hip.conv_igemm(g_up, hc, wc, 2, TAPS_2X2, wT, cu, None, nhwc(g_cur), src_bound=gcat_bound,
+                               dst_bound=gcur_bound)
+                _set_bound(g_cur, gcur_bound)
+            gwT = gbT = colsum = None
+            if need_wT:
+                # ConvT weight grad: rows = convT input, src = g_up gathered with stride 2 (h2: both bounds)
+                # (and its bias grad: the kernel sums the g_up columns it stages, scd_wgrad_t.src_colsum)
+                d, nsplit, nbytes = hip.wgrad_plan(nhwc(cur), g_up, 2, TAPS_2X2, None, cur_bound, gcat_bound)
+                slabs = _empty((nbytes // 4,), cur)
+                if need_bT and _OPTS['convT_bias_in_wgrad'] and hip.wgrad_colsum_supported(d):
+                    colsum = _empty((nsplit * 4 * cto,), cur)
+                    d.src_colsum = colsum.data_ptr()
+                hip.conv_wgrad(d, slabs)
+                gwT = torch.empty_like(convT.weight)
+                hip.wgrad_finalize(slabs, nsplit, cu, 4, cto, 1, cto, gwT)
+            if need_bT:
+                gbT = _empty((cto,), cur)
+                if colsum is not None:
+                    hip.wgrad_colsum_finalize(colsum, nsplit, 4, cto, gbT)
+                else:
+                    hip.channel_sum(g_up, gbT, _ws(hip.bn_workspace_bytes(bb, hh, ww, cto, 1), cur))
+            grads[10 * k:10 * k + 2] = [gwT, gbT]
             g = g_cur
+            if k == 0:
+                g_deep = g_cur
         ctx.saved = None
-        return (None, g, *g_skips, *grads, *head_grads)
+        return (None, g_deep, *g_skips, *grads, *head_grads)
 
 
 def decoder_cat_channels(decoder, n_levels: int) -> dict:
@@ -1506,32 +1609,53 @@ class HeadsFn(torch.autograd.Function):
             return (None,) * (1 + 4 * ns + 2 * len(rows))
         g = g.contiguous()
         pool = _bounds(ys[0])
+        # readers (ctx.needs_input_grad: meta, the sources, (gamma, beta, conv bias) per source, (weight, bias) per head)
+        need_y = _needs(ctx, 1, ns)
+        need_bn = [_needs(ctx, 1 + ns + 3 * i, 3) for i in range(ns)]
+        need_h = [_needs(ctx, 1 + 4 * ns + 2 * j, 2) for j in range(len(rows))]
+        need_hw = any(nh[0] for nh in need_h)  # the stacked weight grad of a source comes from one pass for all heads
         dys, bn_grads, wgs = [], [], []
         for i, (y, src) in enumerate(zip(ys, meta.srcs)):
             st, dc = src.st, src.dc
             assert st.smean is not None  # run_ups(head='raw') keeps the statistics whenever a backward can follow
             bn, conv = dc.conv[4], dc.conv[3]
             n, h, w, c = y.shape
+            ng, nbt, nb = need_bn[i]
+            nb = nb and conv.bias is not None
+            if not (need_y[i] or ng or nbt or nb or need_hw):
+                dys.append(None)
+                bn_grads += [None, None, None]
+                wgs.append(None)
+                continue
             ws_ = wall[:, offs[i]:offs[i] + cs[i]].contiguous()
-            dy = torch.empty_like(y)
-            dgamma, dbeta = _empty((c,), y), _empty((c,), y)
-            dbias = _empty((c,), y) if conv.bias is not None else None
-            wg = _empty((K, c), y)
             db = _take(pool)
-            ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, K), y)
-            hip.bn_relu_backward_head(nhwc(y), g, ws_, K, st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
-                                      dgamma, dbeta, dbias, nhwc(dy), ws, db, wg, frozen=st.frozen)
+            if not need_hw and _bn_through(st, ng, nbt, nb):
+                dy = _bn_backward_through(y, _HeadGrad(g, ws_, K), st, bn, db)
+                dgamma = dbeta = dbias = wg = None
+            else:
+                dy = torch.empty_like(y)
+                dgamma = _empty((c,), y) if ng else None
+                dbeta = _empty((c,), y) if nbt else None
+                dbias = _empty((c,), y) if nb else None
+                wg = _empty((K, c), y) if need_hw else None
+                ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, K) if need_hw else
+                         hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
+                hip.bn_relu_backward_head(nhwc(y), g, ws_, K, st.nseg, st.smean, st.sinv, bn.weight, st.scale,
+                                          st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, db, wg, frozen=st.frozen)
             dys.append(_set_bound(dy, db))
             bn_grads += [dgamma, dbeta, dbias]
             wgs.append(wg)
         y0, st0 = ys[0], meta.srcs[0].st
-        gb = _empty((K,), y0)
-        ws = _ws(hip.conv1x1_workspace_bytes(nhwc(y0), K), y0)
-        hip.conv1x1_bwd_bn(nhwc(y0), st0.scale, st0.shift, st0.nseg, wall[:, :cs[0]].contiguous(), g, K, None, gb, ws)
+        gb = None
+        if any(nh[1] and row[4] for nh, row in zip(need_h, rows)):
+            gb = _empty((K,), y0)
+            ws = _ws(hip.conv1x1_workspace_bytes(nhwc(y0), K), y0)
+            hip.conv1x1_bwd_bn(nhwc(y0), st0.scale, st0.shift, st0.nseg, wall[:, :cs[0]].contiguous(), g, K, None, gb,
+                               ws)
         head_grads = []
-        for k0, no, sel, wshape, has_b in rows:
-            gw = torch.cat([wgs[si][k0:k0 + no] for si in sel], dim=1).reshape(wshape)
-            head_grads += [gw, gb[k0:k0 + no].clone() if has_b else None]
+        for (k0, no, sel, wshape, has_b), (nw, nb) in zip(rows, need_h):
+            gw = torch.cat([wgs[si][k0:k0 + no] for si in sel], dim=1).reshape(wshape) if nw else None
+            head_grads += [gw, gb[k0:k0 + no].clone() if has_b and nb else None]
         return (None, *dys, *bn_grads, *head_grads)
 
 
@@ -1579,11 +1703,12 @@ class HeadFn(torch.autograd.Function):
     def backward(ctx, g):
         x, w2 = ctx.saved_tensors
         n_out = ctx.n_out
-        gx = torch.empty_like(x)
-        gw = _empty(tuple(ctx.wshape), x)
-        gb = _empty((n_out,), x) if ctx.has_bias else None
-        ws = _ws(hip.conv1x1_workspace_bytes(nhwc(x), n_out), x)
-        hip.conv1x1_bwd(nhwc(x), w2, g.contiguous(), n_out, nhwc(gx), False, gw, gb, ws)
+        need_x, need_w, need_b = _needs(ctx, 0, 3)  # a half without a reader is not launched (scd_conv1x1_bwd)
+        gx = torch.empty_like(x) if need_x else None
+        gw = _empty(tuple(ctx.wshape), x) if need_w else None
+        gb = _empty((n_out,), x) if ctx.has_bias and need_b else None
+        ws = _ws(hip.conv1x1_workspace_bytes(nhwc(x), n_out) if gw is not None or gb is not None else 0, x)
+        hip.conv1x1_bwd(nhwc(x), w2, g.contiguous(), n_out, nhwc(gx) if need_x else hip._NULL, False, gw, gb, ws)
         return gx, gw, gb
 
 
@@ -1652,7 +1777,8 @@ class BlockFn(torch.autograd.Function):
         with hip.conv_scope(*meta.scope):
             idx, sv, xshape = ctx.saved
             need_dx = ctx.needs_input_grad[0]
-            gx, pg = _dc_backward(g.contiguous(), sv, meta.dc, need_dx=need_dx, pool=_bounds(g))
+            gx, pg = _dc_backward(g.contiguous(), sv, meta.dc, need_dx=need_dx, pool=_bounds(g),
+                                  need=_needs(ctx, 2, 8))
             if need_dx and meta.maxpool:  # MaxPool2d backward through the argmax bytes
                 gfull = _act(xshape, g)
                 hip.feature_grad(nhwc(gx), idx, hip._NULL, 0, nhwc(gfull))

@@ -256,6 +256,7 @@ _SIGS = {
     "scd_bn_relu_backward_desc": ([POINTER(BNBWDDESC), c_void_p], c_int),
     "scd_input_grad": ([POINTER(INPUTGRAD), c_void_p], c_int),
     "scd_input_grad_supported": ([POINTER(INPUTGRAD)], c_int),
+    "scd_bn_relu_through": ([POINTER(BNBWDDESC), c_void_p], c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -849,6 +850,21 @@ def _bn_backward_frozen(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shi
     for k, v in fields.items():
         setattr(d, k, v)
     _check(lib().scd_bn_relu_backward_desc(ctypes.byref(d), _stream()), "scd_bn_relu_backward_desc")
+
+
+def bn_relu_through(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shift, dy: NHWC, dy_bound=None, **fields):
+    """The backward through a frozen BatchNorm + ReLU none of whose gamma, beta and conv bias in front has a gradient
+    reader (scd_bn_relu_through): dy = gamma*invstd * g*[fma(y, scale, shift) > 0] in one launch, no reduction and no
+    workspace.  `form`: BN_BWD_PLAIN / POOLED / POOLED2 / HEAD; `fields`: the form's own descriptor fields, as
+    _bn_backward_frozen; smean / sinv / scale / shift are bn_frozen_coeffs'."""
+    d = BNBWDDESC()
+    d.form, d.flags, d.y, d.nseg = form, BN_BWD_FROZEN, y, nseg
+    d.mean, d.invstd, d.gamma, d.scale, d.shift = smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), \
+        shift.data_ptr()
+    d.dy, d.dy_bound = dy, _ptr(dy_bound)
+    for k, v in fields.items():
+        setattr(d, k, v)
+    _check(lib().scd_bn_relu_through(ctypes.byref(d), _stream()), "scd_bn_relu_through")
 
 
 def input_grad_desc(dy: NHWC, weight: torch.Tensor, records) -> INPUTGRAD:

@@ -59,6 +59,7 @@ def run_training(cfg, device, max_steps: int | None = None):
     rank, _, world = parallel.env_rank()
     net = networks.create_network(cfg)
     net.to(device)
+    networks.apply_freeze_params(net, cfg)  # TRAINER.FREEZE_PARAMS, once: DDP reads the flags when it builds its buckets
     # TRAINER.EXACT_DATAPARALLEL: the reference's gathered-batch loss of nn.DataParallel (one loss over all ranks'
     # pairs, summed gradients) instead of DDP's mean of per-rank losses (parallel.wrap_ddp)
     net = parallel.wrap_ddp(net, device, exact_dataparallel=bool(cfg.TRAINER.get('EXACT_DATAPARALLEL', False)))

@@ -174,6 +174,44 @@ def apply_freeze_bn(net, cfg):
     return freeze_batchnorm(net, None if v is True else v)
 
 
+def freeze_parameters(net, prefixes=None):
+    """requires_grad_(False) on the parameters of `net`: all of them, or those whose qualified name in the model
+    (`inc.conv.conv.0.weight`, wrappers aside -- no `module.`, as freeze_batchnorm names modules) starts with one of
+    `prefixes`.  Returns the names it froze.  A frozen parameter costs nothing in the backward: its gradient is not
+    formed (no weight grad, no reduction), `p.grad` stays None and AdamW skips it, weight decay included.
+    `.training` is not touched, so this composes with freeze_batchnorm, and the cheapest backward needs both: only a
+    BatchNorm that is in eval mode AND whose gamma, beta and conv bias in front are frozen runs without any reduction
+    (a train-mode BatchNorm needs the gradient's batch statistics whatever trains).  Call it before the model is
+    wrapped for DDP, which reads the flags when it builds its buckets."""
+    if isinstance(prefixes, str):
+        prefixes = [prefixes]
+    prefixes = None if prefixes is None else tuple(str(p) for p in prefixes)
+    frozen = []
+    for name, p in _unwrapped(net).named_parameters():
+        if prefixes is None or name.startswith(prefixes):
+            p.requires_grad_(False)
+            frozen.append(name)
+    return frozen
+
+
+def freeze_params_setting(cfg):
+    """TRAINER.FREEZE_PARAMS (absent: False): False, True (every parameter) or a list of name prefixes."""
+    v = cfg.TRAINER.get('FREEZE_PARAMS', False)
+    if v is None or isinstance(v, bool):
+        return bool(v)
+    if isinstance(v, (list, tuple)) and v and all(isinstance(p, str) for p in v):
+        return [str(p) for p in v]
+    raise ValueError(f"TRAINER.FREEZE_PARAMS must be True, False or a non-empty list of name prefixes, got {v!r}")
+
+
+def apply_freeze_params(net, cfg):
+    """freeze_parameters as TRAINER.FREEZE_PARAMS asks (nothing when it is False or absent).  Returns `net`."""
+    v = freeze_params_setting(cfg)
+    if v is not False:
+        freeze_parameters(net, None if v is True else v)
+    return net
+
+
 def _band_counts(cfg):
     return len(cfg.DATALOADER.S1_BANDS), len(cfg.DATALOADER.S2_BANDS)
 
