@@ -164,7 +164,9 @@ enum scd_conv_math {
  *      Still 11 (symbols appended, nothing existing changes): scd_input_grad and scd_input_grad_supported
  *      (scd_input_grad_t, scd_input_grad_dst_t), the data grad of the channel-padded first layer.
  *      Still 11 (one symbol appended, nothing existing changes): scd_bn_relu_through, the reduction-free backward
- *      through a frozen BatchNorm whose parameters have no gradient reader. */
+ *      through a frozen BatchNorm whose parameters have no gradient reader.
+ *      Still 11 (one symbol appended, nothing existing changes): scd_wgrad_kernel (scd_wgrad_kernel_t, enum
+ *      scd_wgrad_family), the kernel instance and K-split of a weight-grad launch, a host query; no kernel changes. */
 #define SCD_ABI_VERSION 11
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
@@ -425,6 +427,42 @@ int scd_wgrad_colsum_supported(const scd_wgrad_t *d);
  * convolution_backward for ConvTranspose2d. */
 int scd_wgrad_colsum_finalize(float *colsum, int32_t nsplit, int32_t ntaps, int32_t C, float *out,
                               scd_stream_t stream);
+
+/* The kernel instance scd_conv_wgrad would run for `d`, and its K-split.  Decided by the code the launch itself
+ * follows: one function per family fills the choice, and the split plan, scd_wgrad_arith, scd_wgrad_rows_per_block,
+ * the scd_wgrad_*_supported queries, the launch and this query all read it.  Host only, no pointer of the descriptor is
+ * dereferenced (their alignment is read); the one device call is the cached occupancy query the split plan makes
+ * (without a device it falls back to constants), so a test can pin the dispatcher on a machine without a GPU and a GPU
+ * test can assert which instance it is about to check.  Returns 0, or the error scd_conv_wgrad would report for `d`
+ * before launching (other than the slab workspace).  A weight grad run as several launches over image ranges
+ * (operands of 2 GiB and more) reports its first launch; scd_wgrad_plan stays the authority for the slab size. */
+enum scd_wgrad_family {
+    SCD_WGRAD_HALO16 = 0,       /* wgrad_halo16_x3: 16x16x32 MFMA on 2x16 patches with their halo, through registers */
+    SCD_WGRAD_HALO16_DMA = 1,   /* wgrad_halo16_dma: the same block on bf16 storage, patches through an LDS-DMA ring */
+    SCD_WGRAD_HALO16_C16 = 2,   /* wgrad_halo16_c16: the 16-channel source (input layer)                            */
+    SCD_WGRAD_GENERIC_SPLIT = 3, /* wgrad_x3: per-tap gather, x3 / h2 / bf16 (ConvTranspose; 3x3 the halo kernels refuse) */
+    SCD_WGRAD_GENERIC_F32 = 4   /* wgrad_f32: per-tap gather, fp32 MFMA                                             */
+};
+typedef struct scd_wgrad_kernel {
+    int32_t family;         /* enum scd_wgrad_family */
+    int32_t np;             /* arithmetic planes: 1 bf16, 3 x3, 5 x5, 4 h2 (2: h2 without the pre-scaled low term),
+                               0 the fp32 MFMA */
+    int32_t tile;           /* generic families: the tile id 0..4 (128x128, 64x256, 64x192, 64x96, 32x128); else -1 */
+    int32_t block_rows;     /* rows (dY channels) per workgroup: 64 or 128 on the halo kernels, the tile's rows else */
+    int32_t block_channels; /* source channels per workgroup: 64 (halo16), 16 (c16); generic: the tile's (tap, channel)
+                               columns */
+    int32_t layout;         /* halo16 / halo16_dma: 0 = 2x2 waves, 1 = waves along c; else -1 */
+    int32_t sb;             /* bf16 storage */
+    int32_t rows_bn;        /* rows formed through the fused BatchNorm backward (rows_y) */
+    int32_t src_xform;      /* source read through the fused transform (src_scale / src_shift) */
+    int32_t ring;           /* halo16_dma: LDS-DMA ring depth; 0 = patches staged through registers */
+    int32_t threads;        /* threads per workgroup */
+    int32_t nsplit;         /* K-splits of the launch */
+    int32_t kchunk;         /* K units per split: 2x16 patches (halo families: any count, at most one split per 8
+                               patches) or pixels (generic: a multiple of 16); split s covers units
+                               [s * kchunk, min((s + 1) * kchunk, total)) */
+} scd_wgrad_kernel_t;
+int scd_wgrad_kernel(const scd_wgrad_t *d, scd_wgrad_kernel_t *out);
 
 /* ---------------------------------------------------------------------------------------------
  * BatchNorm2d (train: batch statistics per segment; eval: running statistics) + ReLU.

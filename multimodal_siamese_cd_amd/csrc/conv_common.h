@@ -160,24 +160,39 @@ bool igemm_takes_halo16(const IgemmArgs &a);
 bool igemm_takes_c16(const IgemmArgs &a);  // igemm_halo16_c16 (16-channel source)
 bool igemm_takes_gather16(const IgemmArgs &a);  // igemm_gather16, h2 or bf16 (ConvTranspose forward / data grad)
 void launch_halo16(const IgemmArgs &a, int cfg, int tw, hipStream_t s);
-// 16x16x32-MFMA halo weight grad (conv_halo16.hip).
-const void *wgrad_halo16_fn(int math, uint32_t tune, bool bounded, int rblock);  // bounded: h2 under SCD_MATH_H2
-void launch_wgrad_halo16_x3(const WgradArgs &a, dim3 grid, hipStream_t s);
-// Whether the halo weight grad forms its rows through the BatchNorm backward (WgradArgs.rows_y) for this arithmetic.
-bool wgrad16_rows_bn_ok(int math, uint32_t tune, bool bounded);
-// dY rows per block of the halo weight grad (64 or 128; threads = 4 * rows): plan and launch use the same value.
-int wgrad16_rblock(int math, uint32_t tune, int R, bool bounded);
+// The kernel instance a weight-grad launch runs (the fields of scd_wgrad_kernel_t).  wgrad_choose (conv_f32.hip) fills
+// it from the descriptor through one function per family; the split plan, the supported / arith / rows-per-block
+// queries, conv_wgrad_run and the launchers below all read it, and scd_wgrad_kernel reports it: one decision.
+struct WgradKey {  // what of a descriptor decides the instance
+    int math;
+    uint32_t tune;
+    int R, C, ntaps;
+    bool bounded;    // both h2 operand bounds set
+    bool sb;         // bf16 views
+    bool rows_bn;    // rows_y set
+    bool src_xform;  // src_scale / src_shift set
+    int src_nseg;    // source coefficient segments of the launch (with src_xform)
+};
+struct WgradChoice {
+    int family;     // enum scd_wgrad_family
+    int np;         // arithmetic planes (1 bf16, 3 x3, 5 x5, 2 / 4 h2; 0 fp32 MFMA)
+    int tile;       // generic kernels: the kWgradTiles id; -1 otherwise
+    int bm, bn;     // rows (dY channels) per block; source channels (generic: (tap, c) columns) per block
+    int layout;     // halo16: 0 = 2x2 waves, 1 = along c; -1 otherwise
+    int sb, rows_bn, src_xform;
+    int ring;       // LDS-DMA ring depth NB (halo16_dma), 0 = staged through registers
+    int threads;
+    bool rbn_ok;    // the family has a rows-transform (RBN) instantiation for this arithmetic and row block
+};
+// 16x16x32-MFMA halo weight grad (conv_halo16.hip): 3x3 / stride 1 / same size, R and C multiples of 64, maps in 2x16
+// patches.  wgrad16_choose fills the instance (halo16 or halo16_dma), launch_wgrad_halo16_x3 runs it.
+void wgrad16_choose(const WgradKey &q, WgradChoice &k);
+const void *wgrad_halo16_fn(const WgradChoice &k);  // the instance's plain fp32-storage kernel (occupancy query)
+void launch_wgrad_halo16_x3(const WgradArgs &a, const WgradChoice &k, dim3 grid, hipStream_t s);
 // 16-channel-source variant (the input layer), same eligibility otherwise (conv_halo16.hip).
-const void *wgrad_halo16_c16_fn(int math, uint32_t tune, bool bounded);
-int wgrad_c16_planes(int math, uint32_t tune, bool bounded);  // 4 = h2 (both operands bounded), else as the x3 kernels
-void launch_wgrad_halo16_c16(const WgradArgs &a, dim3 grid, hipStream_t s);
-// Halo weight grad (3x3 / stride 1 / same size, R and C multiples of 64, maps in 2x16 patches).
-inline const void *wgrad_halo_fn(int math, uint32_t tune, bool bounded, int rblock) {
-    return wgrad_halo16_fn(math, tune, bounded, rblock);
-}
-inline int wgrad_halo_rblock(int math, uint32_t tune, int R, bool bounded) {
-    return wgrad16_rblock(math, tune, R, bounded);
-}
+void wgrad16_c16_choose(const WgradKey &q, WgradChoice &k);
+const void *wgrad_halo16_c16_fn(const WgradChoice &k);
+void launch_wgrad_halo16_c16(const WgradArgs &a, const WgradChoice &k, dim3 grid, hipStream_t s);
 // x3 weight-grad instantiations, indexed like kWgradTiles (conv_f32.hip).
 const void *wgrad_x3_fn(int tile_id);
 void launch_wgrad_x3(const WgradArgs &a, int tile_id, dim3 grid, dim3 block, hipStream_t s);

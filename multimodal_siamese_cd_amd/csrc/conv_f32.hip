@@ -1050,46 +1050,86 @@ static bool wgrad_c16_ok(const scd_wgrad_t *d) {
 
 // Both operands bounded: the h2 weight grad under SCD_MATH_H2 (x3 otherwise).
 static bool wgrad_bounded(const scd_wgrad_t *d) { return d->rows_bound && d->src_bound; }
+static WgradKey wgrad_key(const scd_wgrad_t *d) {
+    WgradKey q;
+    q.math = d->math;
+    q.tune = d->tune;
+    q.R = d->rows.c;
+    q.C = d->src.c;
+    q.ntaps = d->ntaps;
+    q.bounded = wgrad_bounded(d);
+    q.sb = wgrad_sb(d);
+    q.rows_bn = d->rows_y.data != nullptr;
+    q.src_xform = d->src_scale || d->src_shift;
+    q.src_nseg = d->src_nseg;
+    return q;
+}
+// The generic (non-halo) weight grad: the kWgradTiles entry of least padded work, in
+//   h2   where both bounds are set under SCD_MATH_H2 and the tile has an h2 instantiation (SCD_TUNE_NO_WGRAD_H2
+//        keeps it on x3, A/B),
+//   bf16 for the ConvTranspose weight grad (4 taps) under SCD_MATH_BF16 (the 3x3 weight grads the halo kernels do not
+//        take keep x3), the only generic instance that reads bf16 views,
+//   x3   for every other split arithmetic, and the fp32 MFMA (wgrad_f32) under SCD_MATH_F32.
+static void wgrad_generic_choose(const WgradKey &q, WgradChoice &k) {
+    const WgradTile t = wgrad_tile(q.R, q.ntaps * q.C);
+    k.family = math_split(q.math) ? SCD_WGRAD_GENERIC_SPLIT : SCD_WGRAD_GENERIC_F32;
+    k.np = !math_split(q.math) ? 0
+           : (q.bounded && q.math == SCD_MATH_H2 && !(q.tune & SCD_TUNE_NO_WGRAD_H2) && wgrad_x3_h2_tile(t.id)) ? 4
+           : (q.math == SCD_MATH_BF16 && q.ntaps == 4)                                                          ? 1
+                                                                                                                : 3;
+    k.tile = t.id;
+    k.bm = t.bm;
+    k.bn = t.bn;
+    k.layout = -1;
+    k.sb = q.sb ? 1 : 0;
+    k.rows_bn = q.rows_bn ? 1 : 0;
+    k.src_xform = q.src_xform ? 1 : 0;
+    k.ring = 0;
+    k.threads = t.threads;
+    k.rbn_ok = false;
+}
+// The one decision: which kernel instance `d` runs.
+static void wgrad_choose(const scd_wgrad_t *d, WgradChoice &k) {
+    const WgradKey q = wgrad_key(d);
+    if (wgrad_halo_ok(d))
+        wgrad16_choose(q, k);
+    else if (wgrad_c16_ok(d))
+        wgrad16_c16_choose(q, k);
+    else
+        wgrad_generic_choose(q, k);
+}
+static bool wgrad_is_halo(const WgradChoice &k) { return k.family == SCD_WGRAD_HALO16 || k.family == SCD_WGRAD_HALO16_DMA; }
+static bool wgrad_is_generic(const WgradChoice &k) {
+    return k.family == SCD_WGRAD_GENERIC_SPLIT || k.family == SCD_WGRAD_GENERIC_F32;
+}
+// bf16 views need a kernel that reads them: the bf16 halo16 / c16 instances and the bf16 generic one.
+static bool wgrad_sb_ok(const WgradChoice &k) { return !k.sb || !wgrad_is_generic(k) || k.np == 1; }
 // The halo weight grad with the rows' BatchNorm backward (rows_y) and the dY store (rows_out): its bf16 and h2 along-c
 // variants; h2 in 128-row blocks only (the 64-row h2 block would spill), at most two rows segments per launch.
-static bool wgrad_halo_rbn_ok(const scd_wgrad_t *d) {
-    if (!wgrad_halo_ok(d) || !wgrad16_rows_bn_ok(d->math, d->tune, wgrad_bounded(d))) return false;
-    if (d->math == SCD_MATH_H2 && wgrad_halo_rblock(d->math, d->tune, d->rows.c, true) != 128) return false;
-    return !d->rows_y.data || (d->rows_nseg >= 1 && d->rows_nseg <= 2);
+static bool wgrad_halo_rbn_ok(const scd_wgrad_t *d, const WgradChoice &k) {
+    return wgrad_is_halo(k) && k.rbn_ok && (!d->rows_y.data || (d->rows_nseg >= 1 && d->rows_nseg <= 2));
 }
-// The generic (non-halo) weight grad in h2: bounded, SCD_MATH_H2, a tile with an h2 instantiation.
-// SCD_TUNE_NO_WGRAD_H2 keeps it on x3 (A/B).
-static bool wgrad_generic_h2(const scd_wgrad_t *d) {
-    return wgrad_bounded(d) && d->math == SCD_MATH_H2 && !(d->tune & SCD_TUNE_NO_WGRAD_H2) &&
-           wgrad_x3_h2_tile(wgrad_tile(d->rows.c, d->ntaps * d->src.c).id);
+// The rows transform at all: also the 16-channel-source kernel (no dY store there).
+static bool wgrad_rbn_ok(const scd_wgrad_t *d, const WgradChoice &k) {
+    return k.family == SCD_WGRAD_HALO16_C16 || wgrad_halo_rbn_ok(d, k);
 }
 
-// The generic weight grad in bf16: the ConvTranspose weight grad (4 taps) under SCD_MATH_BF16; the 3x3 weight grads
-// the halo kernels do not take keep x3.
-static bool wgrad_generic_bf16(const scd_wgrad_t *d) { return d->math == SCD_MATH_BF16 && d->ntaps == 4; }
-
-static int wgrad_halo_resident(const scd_wgrad_t *d, bool c16, bool bounded, int rblock) {
-    // per halo weight-grad kernel: 16x16x32 x3 / x5 / bf16 / h2 (x layout); 16-channel x3 / x5 / bf16; the 128-row
-    // bf16 / h2 blocks
+// Blocks of the instance's kernel the whole chip holds at once (occupancy API x CUs), cached per halo weight-grad
+// kernel: 16x16x32 x3 / x5 / bf16 / h2; 16-channel x3 / x5 / bf16 / h2; the 128-row bf16 / h2 blocks.
+static int wgrad_halo_resident(const scd_wgrad_t *d, const WgradChoice &k) {
     static int caches[2][12] = {{0}};
-    const int m = math_planes(d->math);
-    const int planes = m == 1 ? 0 : m == 5 ? 1
-                       : (m == 2 && bounded && (!c16 || wgrad_c16_planes(d->math, d->tune, bounded) == 4)) ? 3
-                                                                                                      : 2;
-    const bool r128 = !c16 && rblock == 128;
+    const bool c16 = k.family == SCD_WGRAD_HALO16_C16;
+    const int planes = k.np == 1 ? 0 : k.np == 5 ? 1 : k.np == 3 ? 2 : 3;
+    const bool r128 = k.bm == 128;
     const int lay = (d->tune & SCD_TUNE_W16_LAYOUT_2X2) ? 1 : 0;
     int &cache = caches[lay][r128 ? 9 + (planes == 3) : c16 ? 5 + planes : 1 + planes];
     if (cache > 0) return cache;
     int per_cu = 0, cus = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu,
-                                                     c16 ? wgrad_halo16_c16_fn(d->math, d->tune, bounded)
-                                                         : wgrad_halo_fn(d->math, d->tune, bounded, rblock),
-                                                     r128 ? 512 : 256, 0) !=
-            hipSuccess ||
-        per_cu < 1 ||
-        cus < 1) {
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c16 ? wgrad_halo16_c16_fn(k) : wgrad_halo16_fn(k),
+                                                     k.threads, 0) != hipSuccess ||
+        per_cu < 1 || cus < 1) {
         (void)hipGetLastError();
         cache = (r128 ? 1 : 2) * 256;  // cached: plan and launch must see the same capacity
         return cache;
@@ -1098,69 +1138,82 @@ static int wgrad_halo_resident(const scd_wgrad_t *d, bool c16, bool bounded, int
     return cache;
 }
 
-static void wgrad_split(const scd_wgrad_t *d, int *nsplit, int *kchunk) {
-    if (wgrad_halo_ok(d) || wgrad_c16_ok(d)) {
-        const bool c16 = !wgrad_halo_ok(d);
-        const int rb = c16 ? 64 : wgrad_halo_rblock(d->math, d->tune, d->rows.c, wgrad_bounded(d));
+// K-splits of the instance `k` over the whole launch.  Halo kernels: 2x16 patches, any count per split, at most one
+// split per 8 patches.  Generic kernels: pixels in multiples of 16 (the K step), at most one split per 256.
+static void wgrad_split(const scd_wgrad_t *d, const WgradChoice &k, int *nsplit, int *kchunk) {
+    if (!wgrad_is_generic(k)) {
         const int64_t patches = pixels(d->rows) / 32;
-        const int64_t tiles = int64_t(d->rows.c / rb) * (c16 ? 1 : d->src.c / 64);
-        split_units(patches, tiles, wgrad_halo_resident(d, c16, wgrad_bounded(d), rb), 8, 1, nsplit, kchunk);
+        const int64_t tiles = int64_t(d->rows.c / k.bm) * (d->src.c / k.bn);
+        // 8 is min_units, not a granule: it caps the splits at ceil(patches / 8); kchunk is any patch count (gran 1)
+        split_units(patches, tiles, wgrad_halo_resident(d, k), 8, 1, nsplit, kchunk);
         return;
     }
     const int Ng = d->ntaps * d->src.c;
-    const WgradTile t = wgrad_tile(d->rows.c, Ng);
+    const WgradTile t = kWgradTiles[k.tile];
     const int64_t tiles = int64_t((d->rows.c + t.bm - 1) / t.bm) * ((Ng + t.bn - 1) / t.bn);
     split_units(pixels(d->rows), tiles, wgrad_resident_blocks(t, d->math), 256, 16, nsplit, kchunk);
+}
+static void wgrad_split(const scd_wgrad_t *d, int *nsplit, int *kchunk) {
+    WgradChoice k;
+    wgrad_choose(d, k);
+    wgrad_split(d, k, nsplit, kchunk);
 }
 }  // namespace scd
 
 namespace scd {
-static bool wgrad_src_bn_ok(const scd_wgrad_t *d) { return wgrad_halo_ok(d) || wgrad_c16_ok(d); }
+// The halo kernels read the source through the fused transform.
+static bool wgrad_src_bn_ok(const WgradChoice &k) { return !wgrad_is_generic(k); }
 // The generic split-arithmetic weight grad (wgrad_x3: the ConvTranspose weight grad) also writes src column sums.
-static bool wgrad_colsum_ok(const scd_wgrad_t *d) {
-    return math_split(d->math) && !wgrad_halo_ok(d) && !wgrad_c16_ok(d) && d->src.c % 4 == 0;
+static bool wgrad_colsum_ok(const scd_wgrad_t *d, const WgradChoice &k) {
+    return k.family == SCD_WGRAD_GENERIC_SPLIT && d->src.c % 4 == 0;
+}
+static int wgrad_arith_of(const WgradChoice &k) {
+    return k.np == 0 ? SCD_MATH_F32 : k.np == 1 ? SCD_MATH_BF16 : k.np == 3 ? SCD_MATH_X3 : k.np == 5 ? SCD_MATH_X5 : SCD_MATH_H2;
 }
 }  // namespace scd
 
 extern "C" int scd_wgrad_colsum_supported(const scd_wgrad_t *d) {
     clear_error();
     if (wgrad_validate(d) != SCD_OK) return 0;
-    return wgrad_colsum_ok(d) ? 1 : 0;
+    WgradChoice k;
+    wgrad_choose(d, k);
+    return wgrad_colsum_ok(d, k) ? 1 : 0;
 }
 
 extern "C" int scd_wgrad_src_bn_supported(const scd_wgrad_t *d) {
     clear_error();
     if (wgrad_validate(d) != SCD_OK) return 0;
-    return wgrad_src_bn_ok(d) ? 1 : 0;
+    WgradChoice k;
+    wgrad_choose(d, k);
+    return wgrad_src_bn_ok(k) ? 1 : 0;
 }
 
 extern "C" int scd_wgrad_rows_bn_supported(const scd_wgrad_t *d) {
     clear_error();
     if (wgrad_validate(d) != SCD_OK) return 0;
-    return wgrad_c16_ok(d) || wgrad_halo_rbn_ok(d) ? 1 : 0;
+    WgradChoice k;
+    wgrad_choose(d, k);
+    return wgrad_rbn_ok(d, k) ? 1 : 0;
 }
 
 extern "C" int scd_wgrad_arith(const scd_wgrad_t *d) {
     clear_error();
     SCD_TRY(wgrad_validate(d));
-    if (!math_split(d->math)) return SCD_MATH_F32;
-    if (wgrad_sb(d) && !wgrad_halo_ok(d) && !wgrad_c16_ok(d) && !wgrad_generic_bf16(d)) {
+    WgradChoice k;
+    wgrad_choose(d, k);
+    if (!wgrad_sb_ok(k)) {
         set_error("wgrad: no bf16-storage kernel takes this shape");
         return SCD_ERR_ARG;
     }
-    if (wgrad_halo_ok(d)) return d->math == SCD_MATH_H2 && !wgrad_bounded(d) ? SCD_MATH_X3 : d->math;
-    if (wgrad_c16_ok(d))
-        return d->math != SCD_MATH_H2 ? d->math
-               : wgrad_c16_planes(d->math, d->tune, wgrad_bounded(d)) == 4 ? SCD_MATH_H2
-                                                                          : SCD_MATH_X3;
-    return wgrad_generic_h2(d) ? SCD_MATH_H2 : wgrad_generic_bf16(d) ? SCD_MATH_BF16 : SCD_MATH_X3;
+    return wgrad_arith_of(k);
 }
 
 extern "C" int scd_wgrad_rows_per_block(const scd_wgrad_t *d) {
     clear_error();
     SCD_TRY(wgrad_validate(d));
-    if (wgrad_halo_ok(d)) return wgrad_halo_rblock(d->math, d->tune, d->rows.c, wgrad_bounded(d));
-    return wgrad_c16_ok(d) ? 64 : 0;
+    WgradChoice k;
+    wgrad_choose(d, k);
+    return wgrad_is_generic(k) ? 0 : k.bm;
 }
 
 namespace scd {
@@ -1253,24 +1306,18 @@ extern "C" int scd_conv_wgrad(const scd_wgrad_t *d, float *slabs, size_t slab_by
 }
 
 namespace scd {
-static int conv_wgrad_run(const scd_wgrad_t *d, float *slabs, size_t slab_bytes, hipStream_t s) {
-    int ns, kc;
-    wgrad_split(d, &ns, &kc);
+// Checks `d` against the instance `k` it runs and fills the kernel arguments (all but slabs and the grid): what
+// conv_wgrad_run launches with and what scd_wgrad_kernel reports errors from.
+static int wgrad_prepare(const scd_wgrad_t *d, const WgradChoice &k, int kc, WgradArgs &a) {
     const int Ng = d->ntaps * d->src.c;
-    const size_t need = size_t(ns) * d->rows.c * Ng * sizeof(float);
-    if (!slabs || slab_bytes < need) {
-        set_error("wgrad: slab workspace %zu < %zu bytes", slab_bytes, need);
-        return SCD_ERR_WORKSPACE;
-    }
-    WgradArgs a;
-    a.sb = wgrad_sb(d) ? 1 : 0;
+    a.sb = k.sb;
     const int eb = elem_size(a.sb);
-    if (d->src_colsum && !wgrad_colsum_ok(d)) {
+    if (d->src_colsum && !wgrad_colsum_ok(d, k)) {
         set_error("wgrad: src_colsum needs the generic split-arithmetic weight grad (check scd_wgrad_colsum_supported)");
         return SCD_ERR_ARG;
     }
     a.colsum = d->src_colsum;
-    if (a.sb && !wgrad_halo_ok(d) && !wgrad_c16_ok(d) && !wgrad_generic_bf16(d)) {
+    if (!wgrad_sb_ok(k)) {
         set_error("wgrad: bf16 views need the bf16 halo16 / c16 / ConvTranspose weight-grad kernels; this shape takes "
                   "none (check scd_wgrad_arith)");
         return SCD_ERR_ARG;
@@ -1292,7 +1339,7 @@ static int conv_wgrad_run(const scd_wgrad_t *d, float *slabs, size_t slab_bytes,
     a.Ng = Ng;
     a.M = int(pixels(d->rows));
     a.kchunk = kc;
-    a.slabs = slabs;
+    a.slabs = nullptr;
     a.div_hw = make_fastdiv(uint32_t(d->rows.h * d->rows.w));
     a.div_w = make_fastdiv(uint32_t(d->rows.w));
     a.div_c = make_fastdiv(uint32_t(d->src.c));
@@ -1325,7 +1372,7 @@ static int conv_wgrad_run(const scd_wgrad_t *d, float *slabs, size_t slab_bytes,
             !d->rows_invstd || !d->rows_scale || !d->rows_shift || !d->rows_coef || !aligned16(d->rows_mean) ||
             !aligned16(d->rows_invstd) || !aligned16(d->rows_scale) || !aligned16(d->rows_shift) ||
             !aligned16(d->rows_coef) || (d->rows_gamma && !aligned16(d->rows_gamma)) ||
-            !(wgrad_c16_ok(d) || wgrad_halo_rbn_ok(d)) || yb >= (int64_t(1) << 31)) {
+            !wgrad_rbn_ok(d, k) || yb >= (int64_t(1) << 31)) {
             set_error("wgrad: the rows BatchNorm backward needs y shaped as rows, rows_nseg | rows.n, 16-byte "
                       "aligned coefficient arrays and a supported shape (check scd_wgrad_rows_bn_supported)");
             return SCD_ERR_ARG;
@@ -1346,7 +1393,7 @@ static int conv_wgrad_run(const scd_wgrad_t *d, float *slabs, size_t slab_bytes,
     a.rows_out_bound = nullptr;
     if (d->rows_out.data) {
         const scd_nhwc_t &o = d->rows_out;
-        if (!d->rows_y.data || !wgrad_halo_rbn_ok(d) || check_view(o, "wgrad.rows_out") != SCD_OK || o.n != d->rows.n ||
+        if (!d->rows_y.data || !wgrad_halo_rbn_ok(d, k) || check_view(o, "wgrad.rows_out") != SCD_OK || o.n != d->rows.n ||
             o.h != d->rows.h || o.w != d->rows.w || o.c != d->rows.c || o.dtype != d->rows.dtype || o.ldc % 4 ||
             (reinterpret_cast<uintptr_t>(o.data) & (a.sb ? 7 : 15))) {
             set_error("wgrad: rows_out needs rows_y on the halo weight grad (scd_wgrad_rows_bn_supported) and a view "
@@ -1359,45 +1406,52 @@ static int conv_wgrad_run(const scd_wgrad_t *d, float *slabs, size_t slab_bytes,
     }
     if (d->src_scale || d->src_shift) {
         if (!d->src_scale || !d->src_shift || d->src_nseg < 1 || d->src.n % d->src_nseg ||
-            !aligned16(d->src_scale) || !aligned16(d->src_shift) || !wgrad_src_bn_ok(d)) {
+            !aligned16(d->src_scale) || !aligned16(d->src_shift) || !wgrad_src_bn_ok(k)) {
             set_error("wgrad: src transform needs both 16-byte aligned coefficient arrays, src_nseg | src.n and a "
                       "supported shape (check scd_wgrad_src_bn_supported)");
             return SCD_ERR_ARG;
         }
         a.src_seg_imgs = d->src.n / d->src_nseg;
     }
-    if (wgrad_halo_ok(d)) {
-        a.n_img_w = d->rows.n;
-        a.grid_r = a.R / wgrad_halo_rblock(a.math, a.tune, a.R, wgrad_bounded(d));
-        a.grid_j = a.C / 64;
-        a.remap = xcd_remap_enabled(a.tune);
-        launch_wgrad_halo16_x3(a, dim3(a.grid_r * a.grid_j * ns), s);
-        return launch_status("scd_conv_wgrad");
-    }
-    if (wgrad_c16_ok(d)) {
-        a.n_img_w = d->rows.n;
-        a.grid_r = a.R / 64;
-        a.grid_j = 1;
-        a.remap = xcd_remap_enabled(a.tune);
-        launch_wgrad_halo16_c16(a, dim3(a.grid_r * ns), s);
-        return launch_status("scd_conv_wgrad");
-    }
-    const WgradTile t = wgrad_tile(a.R, Ng);
-    a.grid_r = (a.R + t.bm - 1) / t.bm;
-    a.grid_j = (Ng + t.bn - 1) / t.bn;
+    a.n_img_w = d->rows.n;
+    a.grid_r = (a.R + k.bm - 1) / k.bm;
+    a.grid_j = wgrad_is_generic(k) ? (Ng + k.bn - 1) / k.bn : a.C / k.bn;
     a.remap = xcd_remap_enabled(a.tune);
-    dim3 grid(a.grid_r * a.grid_j * ns);
-    dim3 block(t.threads);
-    if (math_split(a.math)) {
-        if (wgrad_generic_h2(d))
-            launch_wgrad_x3_h2(a, t.id, grid, block, s);
-        else if (wgrad_generic_bf16(d))
-            launch_wgrad_x3_bf16(a, t.id, grid, block, s);
-        else
-            launch_wgrad_x3(a, t.id, grid, block, s);
+    return SCD_OK;
+}
+
+static int conv_wgrad_run(const scd_wgrad_t *d, float *slabs, size_t slab_bytes, hipStream_t s) {
+    WgradChoice k;
+    wgrad_choose(d, k);
+    int ns, kc;
+    wgrad_split(d, k, &ns, &kc);
+    const size_t need = size_t(ns) * d->rows.c * d->ntaps * d->src.c * sizeof(float);
+    if (!slabs || slab_bytes < need) {
+        set_error("wgrad: slab workspace %zu < %zu bytes", slab_bytes, need);
+        return SCD_ERR_WORKSPACE;
+    }
+    WgradArgs a;
+    SCD_TRY(wgrad_prepare(d, k, kc, a));
+    a.slabs = slabs;
+    const dim3 grid(a.grid_r * a.grid_j * ns), block(k.threads);
+    if (wgrad_is_halo(k)) {
+        launch_wgrad_halo16_x3(a, k, grid, s);
         return launch_status("scd_conv_wgrad");
     }
-    switch (t.id) {
+    if (k.family == SCD_WGRAD_HALO16_C16) {
+        launch_wgrad_halo16_c16(a, k, grid, s);
+        return launch_status("scd_conv_wgrad");
+    }
+    if (k.family == SCD_WGRAD_GENERIC_SPLIT) {
+        if (k.np == 4)
+            launch_wgrad_x3_h2(a, k.tile, grid, block, s);
+        else if (k.np == 1)
+            launch_wgrad_x3_bf16(a, k.tile, grid, block, s);
+        else
+            launch_wgrad_x3(a, k.tile, grid, block, s);
+        return launch_status("scd_conv_wgrad");
+    }
+    switch (k.tile) {
         case 0: hipLaunchKernelGGL((wgrad_f32<2, 2, 2, 2, 16>), grid, block, 0, s, a); break;
         case 1: hipLaunchKernelGGL((wgrad_f32<1, 4, 2, 2, 16>), grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL((wgrad_f32<2, 2, 1, 3, 16>), grid, block, 0, s, a); break;
@@ -1407,6 +1461,42 @@ static int conv_wgrad_run(const scd_wgrad_t *d, float *slabs, size_t slab_bytes,
     return launch_status("scd_conv_wgrad");
 }
 }  // namespace scd
+
+extern "C" int scd_wgrad_kernel(const scd_wgrad_t *d, scd_wgrad_kernel_t *out) {
+    clear_error();
+    if (!d || !out) {
+        set_error("scd_wgrad_kernel: null argument");
+        return SCD_ERR_ARG;
+    }
+    SCD_TRY(wgrad_validate(d));
+    const int chunk = wgrad_chunk(d);
+    if (chunk < 1) {
+        set_error("wgrad: one image of the operands spans 2 GiB or more (32-bit buffer offsets)");
+        return SCD_ERR_ARG;
+    }
+    // a weight grad run in image chunks: the first launch's instance and split
+    const scd_wgrad_t c = chunk < d->rows.n ? wgrad_slice(d, 0, chunk) : *d;
+    WgradChoice k;
+    wgrad_choose(&c, k);
+    int ns, kc;
+    wgrad_split(&c, k, &ns, &kc);
+    WgradArgs a;
+    SCD_TRY(wgrad_prepare(&c, k, kc, a));
+    out->family = k.family;
+    out->np = k.np;
+    out->tile = k.tile;
+    out->block_rows = k.bm;
+    out->block_channels = k.bn;
+    out->layout = k.layout;
+    out->sb = k.sb;
+    out->rows_bn = k.rows_bn;
+    out->src_xform = k.src_xform;
+    out->ring = k.ring;
+    out->threads = k.threads;
+    out->nsplit = ns;
+    out->kchunk = kc;
+    return SCD_OK;
+}
 
 namespace scd {
 // scd_wgrad_colsum_finalize, two fixed-order stages: (1) in place, split group g's 16 rows summed in split order into

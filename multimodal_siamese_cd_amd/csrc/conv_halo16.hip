@@ -2407,13 +2407,25 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo16_c16(WgradArgs a) {
 static int wgrad16_planes(int math, uint32_t tune, bool bounded) {
     return math_planes(math) == 2 ? (bounded ? (h2_prescale(tune) ? 4 : 2) : 3) : math_planes(math);
 }
-// The 16-channel kernel's arithmetic: h2 with the pre-scaled low term only (SCD_TUNE_H2_NO_PRESCALE keeps it on x3).
-int wgrad_c16_planes(int math, uint32_t tune, bool bounded) {
-    const int np = wgrad16_planes(math, tune, bounded);
-    return np == 2 ? 3 : np;
+// The 16-channel kernel: h2 with the pre-scaled low term only (SCD_TUNE_H2_NO_PRESCALE keeps it on x3); one block is
+// 64 rows by the 16 channels, four waves along r; every arithmetic has the rows transform, bf16 also bf16 storage.
+void wgrad16_c16_choose(const WgradKey &q, WgradChoice &k) {
+    const int np = wgrad16_planes(q.math, q.tune, q.bounded);
+    k.family = SCD_WGRAD_HALO16_C16;
+    k.np = np == 2 ? 3 : np;
+    k.tile = -1;
+    k.bm = 64;
+    k.bn = 16;
+    k.layout = -1;
+    k.sb = q.sb ? 1 : 0;
+    k.rows_bn = q.rows_bn ? 1 : 0;
+    k.src_xform = q.src_xform ? 1 : 0;
+    k.ring = 0;
+    k.threads = 256;
+    k.rbn_ok = true;
 }
-const void *wgrad_halo16_c16_fn(int math, uint32_t tune, bool bounded) {
-    switch (wgrad_c16_planes(math, tune, bounded)) {
+const void *wgrad_halo16_c16_fn(const WgradChoice &k) {
+    switch (k.np) {
         case 1: return reinterpret_cast<const void *>(&wgrad_halo16_c16<1, false>);
         case 4: return reinterpret_cast<const void *>(&wgrad_halo16_c16<4, false>);
         case 5: return reinterpret_cast<const void *>(&wgrad_halo16_c16<5, false>);
@@ -2421,10 +2433,10 @@ const void *wgrad_halo16_c16_fn(int math, uint32_t tune, bool bounded) {
     }
 }
 template <bool RBN>
-static void launch_c16(const WgradArgs &a, dim3 grid, hipStream_t s) {
-    switch (wgrad_c16_planes(a.math, a.tune, a.rows_bound && a.src_bound)) {
+static void launch_c16(const WgradArgs &a, const WgradChoice &k, dim3 grid, hipStream_t s) {
+    switch (k.np) {
         case 1:
-            if (a.sb)
+            if (k.sb)
                 hipLaunchKernelGGL((wgrad_halo16_c16<1, RBN, true>), grid, dim3(256), 0, s, a);
             else
                 hipLaunchKernelGGL((wgrad_halo16_c16<1, RBN>), grid, dim3(256), 0, s, a);
@@ -2434,21 +2446,50 @@ static void launch_c16(const WgradArgs &a, dim3 grid, hipStream_t s) {
         default: hipLaunchKernelGGL((wgrad_halo16_c16<3, RBN>), grid, dim3(256), 0, s, a);
     }
 }
-void launch_wgrad_halo16_c16(const WgradArgs &a, dim3 grid, hipStream_t s) {
-    if (a.rows_y)
-        launch_c16<true>(a, grid, s);
+void launch_wgrad_halo16_c16(const WgradArgs &a, const WgradChoice &k, dim3 grid, hipStream_t s) {
+    if (k.rows_bn)
+        launch_c16<true>(a, k, grid, s);
     else
-        launch_c16<false>(a, grid, s);
+        launch_c16<false>(a, k, grid, s);
 }
 // Wave layout of the h2 and bf16 variants (W16L): SCD_TUNE_W16_LAYOUT_2X2 keeps the 2x2 layout, default along c.
 // x3 / x5 keep 2x2: their third dY plane does not fit four r blocks in registers.
 static int w16_layout(uint32_t tune) { return (tune & SCD_TUNE_W16_LAYOUT_2X2) ? 0 : 1; }
-// Rows of dY per block: 128 (RG 2) for the h2 / bf16 variants in the along-c layout when R % 128 == 0, else 64
-// (SCD_TUNE_WGRAD_R64: always 64; plan and launch see the same descriptor bits).
-int wgrad16_rblock(int math, uint32_t tune, int R, bool bounded) {
-    const int np = wgrad16_planes(math, tune, bounded);
-    if (!(np == 1 || np == 2 || np == 4) || !w16_layout(tune) || R % 128) return 64;
-    return (tune & SCD_TUNE_WGRAD_R64) ? 64 : 128;
+// Ring depth NB of the wgrad_halo16_dma instance for a row block (RG), source transform (XT) and rows transform (RBN):
+// the choice reports it and the launch instantiates with it.
+static constexpr int w16_dma_ring(int rg, bool xt, bool rbn) {
+    return rbn ? (rg == 2 ? 5 : 3) : (xt && rg == 2) ? SCD_WGRAD16_DMA_NB_XT : SCD_WGRAD16_DMA_NB;
+}
+// The halo weight grad's instance.
+//   planes : h2 where both operands are bounded, x3 otherwise under SCD_MATH_H2 (wgrad16_planes).
+//   layout : h2 / bf16 along c unless SCD_TUNE_W16_LAYOUT_2X2; x3 / x5 always 2x2.
+//   rows   : 128 (RG 2, 512 threads) for the h2 / bf16 variants in the along-c layout when R % 128 == 0, else 64
+//            (SCD_TUNE_WGRAD_R64: always 64).
+//   rows transform (rows_y): h2 with the pre-scaled low term in 128-row blocks, or bf16, along c (rbn_ok).
+//   bf16 storage: the LDS-DMA ring (halo16_dma) in the along-c layout unless SCD_TUNE_WGRAD16_REGSTAGE; with a source
+//            transform only for at most two source segments (and SCD_WGRAD16_DMA_TRANSFORMS builds), with the rows
+//            transform only in SCD_WGRAD16_DMA_TRANSFORMS builds; otherwise staged through registers.
+void wgrad16_choose(const WgradKey &q, WgradChoice &k) {
+    const int np = wgrad16_planes(q.math, q.tune, q.bounded);
+    const bool wide = np == 1 || np == 2 || np == 4;
+    k.family = SCD_WGRAD_HALO16;
+    k.np = np;
+    k.tile = -1;
+    k.layout = wide ? w16_layout(q.tune) : 0;
+    k.bm = (wide && k.layout && q.R % 128 == 0 && !(q.tune & SCD_TUNE_WGRAD_R64)) ? 128 : 64;
+    k.bn = 64;
+    k.sb = q.sb ? 1 : 0;
+    k.rows_bn = q.rows_bn ? 1 : 0;
+    k.src_xform = q.src_xform ? 1 : 0;
+    k.ring = 0;
+    k.threads = 4 * k.bm;
+    k.rbn_ok = k.layout == 1 && (np == 1 || (np == 4 && k.bm == 128));
+    const bool two_seg = !q.src_xform || q.src_nseg <= 2;
+    if (np == 1 && q.sb && k.layout && !(q.tune & SCD_TUNE_WGRAD16_REGSTAGE) && two_seg &&
+        (SCD_WGRAD16_DMA_TRANSFORMS || !(q.src_xform || q.rows_bn))) {
+        k.family = SCD_WGRAD_HALO16_DMA;
+        k.ring = w16_dma_ring(k.bm / 64, q.src_xform, q.rows_bn);
+    }
 }
 template <int NP>
 static const void *w16_kernel(int lc, int rb) {
@@ -2465,17 +2506,16 @@ static void w16_launch(int lc, int rb, const WgradArgs &a, dim3 grid, hipStream_
     else
         hipLaunchKernelGGL((wgrad_halo16_x3<NP, 0, 1, SB>), grid, dim3(256), 0, s, a);
 }
-const void *wgrad_halo16_fn(int math, uint32_t tune, bool bounded, int rblock) {
-    switch (wgrad16_planes(math, tune, bounded)) {
-        case 1: return w16_kernel<1>(w16_layout(tune), rblock);
-        case 2: return w16_kernel<2>(w16_layout(tune), rblock);
-        case 4: return w16_kernel<4>(w16_layout(tune), rblock);
+const void *wgrad_halo16_fn(const WgradChoice &k) {
+    switch (k.np) {
+        case 1: return w16_kernel<1>(k.layout, k.bm);
+        case 2: return w16_kernel<2>(k.layout, k.bm);
+        case 4: return w16_kernel<4>(k.layout, k.bm);
         case 5: return reinterpret_cast<const void *>(&wgrad_halo16_x3<5, 0, 1>);
         default: return reinterpret_cast<const void *>(&wgrad_halo16_x3<3, 0, 1>);
     }
 }
-// The rows transform (a.rows_y): h2 with the pre-scaled low term, or bf16, in the along-c layout
-// (wgrad16_rows_bn_ok); both row-block sizes.
+// The rows transform (k.rows_bn; the caller checked rbn_ok): along c, both row-block sizes.
 template <int NP, bool SB>
 static void w16_launch_rbn(int rb, const WgradArgs &a, dim3 grid, hipStream_t s) {
     if (rb == 128)
@@ -2483,57 +2523,55 @@ static void w16_launch_rbn(int rb, const WgradArgs &a, dim3 grid, hipStream_t s)
     else
         hipLaunchKernelGGL((wgrad_halo16_x3<NP, 1, 1, SB, true>), grid, dim3(256), 0, s, a);
 }
-bool wgrad16_rows_bn_ok(int math, uint32_t tune, bool bounded) {
-    const int np = wgrad16_planes(math, tune, bounded);
-    return (np == 1 || np == 4) && w16_layout(tune);
-}
-// a.grid_r = R / wgrad16_rblock(...) (the caller plans with the same choice).
-void launch_wgrad_halo16_x3(const WgradArgs &a, dim3 grid, hipStream_t s) {
-    const bool bounded = a.rows_bound && a.src_bound;
-    const int lc = w16_layout(a.tune), rb = wgrad16_rblock(a.math, a.tune, a.R, bounded);
-    if (a.rows_y) {  // the caller checked wgrad16_rows_bn_ok
-        if (wgrad16_planes(a.math, a.tune, bounded) == 4)
-            w16_launch_rbn<4, false>(rb, a, grid, s);
-        else if (SCD_WGRAD16_DMA_TRANSFORMS && a.sb && !(a.tune & SCD_TUNE_WGRAD16_REGSTAGE) &&
-                 (!a.src_scale || a.n_img_w / a.src_seg_imgs <= 2)) {
-            // bf16 storage: the LDS-DMA ring with y and dL/da landed raw and dY formed in place (+ the source transform)
-            if (rb == 128) {
-                if (a.src_scale)
-                    hipLaunchKernelGGL((wgrad_halo16_dma<2, 5, true, true>), grid, dim3(512), 0, s, a);
+// Runs the instance `k` (wgrad16_choose); a.grid_r = R / k.bm.  halo16_dma, bf16 storage through the LDS-DMA ring: y and
+// dL/da landed raw and dY formed in place (RBN), the source transform in place (XT); same residency as the
+// register-staged kernel (one 512-thread block / two 256-thread blocks per CU), so the split plan is the same.
+void launch_wgrad_halo16_x3(const WgradArgs &a, const WgradChoice &k, dim3 grid, hipStream_t s) {
+    const bool dma = k.family == SCD_WGRAD_HALO16_DMA;
+    if (k.rows_bn) {  // the caller checked rbn_ok
+        if (k.np == 4)
+            w16_launch_rbn<4, false>(k.bm, a, grid, s);
+        else if (dma) {
+            if (k.bm == 128) {
+                if (k.src_xform)
+                    hipLaunchKernelGGL((wgrad_halo16_dma<2, w16_dma_ring(2, true, true), true, true>), grid, dim3(512), 0,
+                                       s, a);
                 else
-                    hipLaunchKernelGGL((wgrad_halo16_dma<2, 5, false, true>), grid, dim3(512), 0, s, a);
-            } else if (a.src_scale)
-                hipLaunchKernelGGL((wgrad_halo16_dma<1, 3, true, true>), grid, dim3(256), 0, s, a);
+                    hipLaunchKernelGGL((wgrad_halo16_dma<2, w16_dma_ring(2, false, true), false, true>), grid, dim3(512),
+                                       0, s, a);
+            } else if (k.src_xform)
+                hipLaunchKernelGGL((wgrad_halo16_dma<1, w16_dma_ring(1, true, true), true, true>), grid, dim3(256), 0, s,
+                                   a);
             else
-                hipLaunchKernelGGL((wgrad_halo16_dma<1, 3, false, true>), grid, dim3(256), 0, s, a);
-        } else if (a.sb)
-            w16_launch_rbn<1, true>(rb, a, grid, s);
+                hipLaunchKernelGGL((wgrad_halo16_dma<1, w16_dma_ring(1, false, true), false, true>), grid, dim3(256), 0,
+                                   s, a);
+        } else if (k.sb)
+            w16_launch_rbn<1, true>(k.bm, a, grid, s);
         else
-            w16_launch_rbn<1, false>(rb, a, grid, s);
+            w16_launch_rbn<1, false>(k.bm, a, grid, s);
         return;
     }
-    switch (wgrad16_planes(a.math, a.tune, bounded)) {
+    switch (k.np) {
         case 1:
-            if (a.sb && lc && !(a.tune & SCD_TUNE_WGRAD16_REGSTAGE) &&
-                (!a.src_scale || (SCD_WGRAD16_DMA_TRANSFORMS && a.n_img_w / a.src_seg_imgs <= 2))) {
-                // bf16 storage: the LDS-DMA ring (same residency as the register-staged kernel: one 512-thread block /
-                // two 256-thread blocks per CU, so the split plan is unchanged); a source transform in place
-                if (a.src_scale) {
-                    if (rb == 128)
-                        hipLaunchKernelGGL((wgrad_halo16_dma<2, SCD_WGRAD16_DMA_NB_XT, true>), grid, dim3(512), 0, s, a);
+            if (dma) {
+                if (k.src_xform) {
+                    if (k.bm == 128)
+                        hipLaunchKernelGGL((wgrad_halo16_dma<2, w16_dma_ring(2, true, false), true>), grid, dim3(512), 0,
+                                           s, a);
                     else
-                        hipLaunchKernelGGL((wgrad_halo16_dma<1, SCD_WGRAD16_DMA_NB, true>), grid, dim3(256), 0, s, a);
-                } else if (rb == 128)
-                    hipLaunchKernelGGL((wgrad_halo16_dma<2, SCD_WGRAD16_DMA_NB>), grid, dim3(512), 0, s, a);
+                        hipLaunchKernelGGL((wgrad_halo16_dma<1, w16_dma_ring(1, true, false), true>), grid, dim3(256), 0,
+                                           s, a);
+                } else if (k.bm == 128)
+                    hipLaunchKernelGGL((wgrad_halo16_dma<2, w16_dma_ring(2, false, false)>), grid, dim3(512), 0, s, a);
                 else
-                    hipLaunchKernelGGL((wgrad_halo16_dma<1, SCD_WGRAD16_DMA_NB>), grid, dim3(256), 0, s, a);
-            } else if (a.sb)
-                w16_launch<1, true>(lc, rb, a, grid, s);
+                    hipLaunchKernelGGL((wgrad_halo16_dma<1, w16_dma_ring(1, false, false)>), grid, dim3(256), 0, s, a);
+            } else if (k.sb)
+                w16_launch<1, true>(k.layout, k.bm, a, grid, s);
             else
-                w16_launch<1>(lc, rb, a, grid, s);
+                w16_launch<1>(k.layout, k.bm, a, grid, s);
             break;
-        case 2: w16_launch<2>(lc, rb, a, grid, s); break;
-        case 4: w16_launch<4>(lc, rb, a, grid, s); break;
+        case 2: w16_launch<2>(k.layout, k.bm, a, grid, s); break;
+        case 4: w16_launch<4>(k.layout, k.bm, a, grid, s); break;
         case 5: hipLaunchKernelGGL((wgrad_halo16_x3<5, 0, 1>), grid, dim3(256), 0, s, a); break;
         default: hipLaunchKernelGGL((wgrad_halo16_x3<3, 0, 1>), grid, dim3(256), 0, s, a);
     }

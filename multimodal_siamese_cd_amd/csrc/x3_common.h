@@ -41,7 +41,8 @@ __device__ __forceinline__ void split3(const f32x4 v, u32x2 &h, u32x2 &m, u32x2 
 // to U * s < 2^15 (< fp16 max 65504); x * s = h + m with h = fp16(x * s) and m = fp16(x * s - h), both rounded
 // to nearest.  The subtraction is exact, h and m carry 11 significant bits each, so h + m represents x * s to
 // 2^-22 relative while m stays in the fp16 normal range (x * s >= 2^-3), with a floor of 2^-25 absolute
-// below.  A product keeps hh + hm + mh (the dropped mm is <= 2^-24 relative): three MFMAs against x3's six.
+// below.  A product keeps hh + hm + mh (the dropped mm is <= 2^-22 relative: |m| <= 2^-11 |x| on each operand):
+// three MFMAs against x3's six.
 //
 // Activations and gradients can span far more than the 2^17 binades above that floor (a few large gradient
 // values over a bulk 2^20 below them), so their low term is kept pre-scaled: m' = fp16((x * s - h) * 2^11),

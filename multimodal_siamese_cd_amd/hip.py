@@ -132,6 +132,15 @@ class WGRAD(ctypes.Structure):
     ]
 
 
+class WGRADKERNEL(ctypes.Structure):
+    """scd_wgrad_kernel_t: the kernel instance and K-split scd_conv_wgrad runs for a descriptor."""
+
+    _fields_ = [("family", c_int32), ("np", c_int32), ("tile", c_int32), ("block_rows", c_int32),
+                ("block_channels", c_int32), ("layout", c_int32), ("sb", c_int32), ("rows_bn", c_int32),
+                ("src_xform", c_int32), ("ring", c_int32), ("threads", c_int32), ("nsplit", c_int32),
+                ("kchunk", c_int32)]
+
+
 # Tap sets (dy, dx) used by the network.
 TAPS_3X3 = ([-1, -1, -1, 0, 0, 0, 1, 1, 1], [-1, 0, 1, -1, 0, 1, -1, 0, 1])  # t = ky*3 + kx
 TAPS_1 = ([0], [0])
@@ -171,6 +180,7 @@ _SIGS = {
     "scd_wgrad_rows_bn_supported": ([POINTER(WGRAD)], c_int),
     "scd_wgrad_finalize": ([c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p], c_int),
     "scd_wgrad_colsum_supported": ([POINTER(WGRAD)], c_int),
+    "scd_wgrad_kernel": ([POINTER(WGRAD), POINTER(WGRADKERNEL)], c_int),
     "scd_wgrad_colsum_finalize": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], c_int),
     "scd_bn_workspace_bytes": ([c_int32, c_int32, c_int32, c_int32, c_int32], c_size_t),
     "scd_bn_train_stats": (
@@ -758,6 +768,34 @@ def wgrad_plan(rows: NHWC, src: NHWC, stride: int, taps, src_bn=None, rows_bound
     nb = c_size_t(0)
     _check(lib().scd_wgrad_plan(ctypes.byref(d), ctypes.byref(ns), ctypes.byref(nb)), "scd_wgrad_plan")
     return d, ns.value, nb.value
+
+
+# enum scd_wgrad_family; WgradKernel.layout
+WGRAD_FAMILIES = ('halo16', 'halo16_dma', 'halo16_c16', 'generic_split', 'generic_f32')
+WGRAD_LAYOUTS = {0: '2x2', 1: 'along_c', -1: None}
+WgradKernel = collections.namedtuple(
+    'WgradKernel', 'family np tile block_rows block_channels layout sb rows_bn src_xform ring threads nsplit kchunk')
+
+
+def wgrad_kernel_of(d: 'WGRAD') -> WgradKernel:
+    """scd_wgrad_kernel for a built descriptor: the instance scd_conv_wgrad would run and its K-split (host only)."""
+    k = WGRADKERNEL()
+    _check(lib().scd_wgrad_kernel(ctypes.byref(d), ctypes.byref(k)), "scd_wgrad_kernel")
+    return WgradKernel(WGRAD_FAMILIES[k.family], k.np, k.tile, k.block_rows, k.block_channels,
+                       WGRAD_LAYOUTS[k.layout], bool(k.sb), bool(k.rows_bn), bool(k.src_xform), k.ring, k.threads,
+                       k.nsplit, k.kchunk)
+
+
+def wgrad_kernel(rows: NHWC, src: NHWC, stride: int, taps, src_bn=None, rows_bound=None, src_bound=None,
+                 rows_bn=None, rows_out: NHWC | None = None, rows_out_bound=None) -> WgradKernel:
+    """The kernel instance conv_wgrad would run for the descriptor wgrad_plan builds from the same arguments."""
+    d = wgrad_desc(rows, src, stride, taps, src_bn, rows_bound, src_bound)
+    if rows_bn is not None:
+        _rows_bn_fields(d, rows_bn)
+    if rows_out is not None:
+        d.rows_out = rows_out
+        d.rows_out_bound = _ptr(rows_out_bound)
+    return wgrad_kernel_of(d)
 
 
 def wgrad_src_bn_supported(rows: NHWC, src: NHWC, stride: int, taps, src_bn) -> bool:
