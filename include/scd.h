@@ -166,7 +166,9 @@ enum scd_conv_math {
  *      Still 11 (one symbol appended, nothing existing changes): scd_bn_relu_through, the reduction-free backward
  *      through a frozen BatchNorm whose parameters have no gradient reader.
  *      Still 11 (one symbol appended, nothing existing changes): scd_wgrad_kernel (scd_wgrad_kernel_t, enum
- *      scd_wgrad_family), the kernel instance and K-split of a weight-grad launch, a host query; no kernel changes. */
+ *      scd_wgrad_family), the kernel instance and K-split of a weight-grad launch, a host query; no kernel changes.
+ *      Still 11 (symbols appended, nothing existing changes): scd_bn_stats_local, scd_bn_stats_from_ranks,
+ *      scd_bn_relu_backward_sums and scd_bn_relu_backward_from_sums, BatchNorm synchronized over ranks. */
 #define SCD_ABI_VERSION 11
 int scd_abi_version(void);
 /* The arithmetic scd_conv_igemm / scd_conv_wgrad will use for a descriptor (its `math`, or SCD_MATH_X3 / F32 where
@@ -641,6 +643,49 @@ int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream);
  * replaces: the backward of networks.py:393-394,396-397 under eval-mode BatchNorm with frozen parameters, where
  * autograd forms neither batch-norm statistic nor parameter gradient. */
 int scd_bn_relu_through(const scd_bn_bwd_t *d, scd_stream_t stream);
+
+/* BatchNorm synchronized over data-parallel ranks: one set of batch statistics over the batch of all ranks, and the
+ * backward differentiated through them (torch.nn.SyncBatchNorm).  The library issues no collective; each direction is
+ * cut in two at the point where the ranks' small double records meet, and the caller gathers them in between:
+ *
+ *   forward   scd_bn_stats_local      -> stat [nseg][c][3] = {n, mean, M2} of this rank      (gather over ranks)
+ *             scd_bn_stats_from_ranks <- stats [nranks][nseg][c][3]
+ *   backward  scd_bn_relu_backward_sums      -> sums [nseg][c][2] = {sum dz, sum dz*xhat}    (gather over ranks)
+ *             scd_bn_relu_backward_from_sums <- sums [nranks][nseg][c][2], and the forward's gathered stats
+ *
+ * The halves are the kernels of scd_bn_train_stats / scd_bn_stats_from_tiles and scd_bn_relu_backward_desc cut at that
+ * point, with their summation orders: with nranks = 1 each pair is bit-identical to the entry point it was cut from.
+ * Records are merged in rank order on every rank, so the coefficients and the running statistics are bit-identical
+ * across ranks.  Counts travel in the records: ranks may hold different numbers of images (at least one each).
+ * Every check runs on the host before any launch; an error reads "sync: ...".
+ *
+ * scd_bn_stats_local: the partial pass over y (tile_rec NULL; workspace scd_bn_workspace_bytes), or the merge of the
+ * conv-epilogue tile records as scd_bn_stats_from_tiles (then only y.c is read; workspace
+ * scd_bn_tile_stats_workspace_bytes), then the fixed-order double merge per segment and channel.
+ * scd_bn_stats_from_ranks: Chan merge of the ranks' records, then scd_bn_train_stats' arithmetic and outputs with the
+ * global count (invstd, scale, shift, the running update with the unbiased global variance, act_bound). */
+int scd_bn_stats_local(scd_nhwc_t y, const float *tile_rec, int32_t ntiles, int32_t tile_pixels, int32_t nseg,
+                       double *stat, void *ws, size_t ws_bytes, scd_stream_t stream);
+int scd_bn_stats_from_ranks(const double *stats, int32_t nranks, int32_t c, int32_t nseg, const float *gamma,
+                            const float *beta, float eps, float momentum, int32_t update_running, float *running_mean,
+                            float *running_var, float *save_mean, float *save_invstd, float *scale, float *shift,
+                            float *act_bound, scd_stream_t stream);
+/* The backward, for every form of scd_bn_bwd_t; both calls take the same descriptor, whose mean / invstd / scale /
+ * shift are scd_bn_stats_from_ranks'.
+ * _sums: the form's partial pass (or its tile records: _TILES, _COEF with tile_rec) and the record sums of this rank.
+ *   Writes none of the descriptor's outputs but w_grad (_HEAD): the head's weight grad is rank-local and comes out of
+ *   this call's partial pass; _from_sums ignores the field.
+ * _from_sums: k1, k2 = the ranks' sums added in rank order / the global count (the sum of the ranks' stats[.][0]);
+ *   then the form's apply walk, unchanged (_COEF: coef, and dy_bound from the statistics with the global count).
+ *   dgamma, dbeta: from this rank's own sums (the caller's gradient reduction adds the ranks', like any parameter's).
+ *   dbias_prev: this rank's sum of dy, no longer ~0 per rank but only over all ranks; the applying forms sum dy as
+ *   they store it, _COEF forms it as gamma*invstd*(S1 - n*k1 - k2*X) with this rank's S1, count n and
+ *   X = sum xhat = n*(mean_rank - mean)*invstd from stats[rank].
+ * SCD_BN_BWD_FROZEN is refused (a BatchNorm on its running statistics has nothing to synchronize), as are null
+ * pointers, nranks < 1 and a rank outside [0, nranks). */
+int scd_bn_relu_backward_sums(const scd_bn_bwd_t *d, double *sums, scd_stream_t stream);
+int scd_bn_relu_backward_from_sums(const scd_bn_bwd_t *d, const double *sums, const double *stats, int32_t nranks,
+                                   int32_t rank, scd_stream_t stream);
 
 /* out[c] = sum over all pixels of x[., c] (ConvTranspose2d bias grad, networks.py:433); workspace as
  * scd_bn_workspace_bytes(n, h, w, c, 1).  replaces: the bias-grad reduction of convolution_backward. */

@@ -212,6 +212,38 @@ __device__ __forceinline__ float bn_act_bound(double n, double gamma, double bet
     return float((dev + fabs(beta)) * (1.0 + 0x1p-10) + (fabs(shift) + fabs(beta)) * 0x1p-16);
 }
 
+// The two halves of bn_stats_finalize, which the synchronized BatchNorm runs with a gather of the ranks' records in
+// between (bn_stats_local_kernel / bn_stats_from_ranks_kernel).
+// Segment s of channel c's chunk records (rc), merged in double in the block's fixed order; valid in thread 0.
+__device__ __forceinline__ DWelford bn_seg_merge(const float *rc, int s, int ncps, DWelford *sh) {
+    DWelford w{0, 0, 0};
+    for (int k = threadIdx.x; k < ncps; k += BN_THREADS) {
+        const float *r = rc + size_t(s * ncps + k) * 3;
+        dmerge(w, DWelford{r[0], r[1], r[2]});
+    }
+    return block_dmerge(w, sh);
+}
+// Everything a BatchNorm takes from segment s' merged statistics a of channel c (one thread; segments in order).
+__device__ __forceinline__ void bn_stats_emit(const DWelford &a, int s, int c, int C, const float *gamma,
+                                              const float *beta, float eps, float momentum, int update, float *rmean,
+                                              float *rvar, float *smean, float *sinv, float *scale, float *shift,
+                                              float *act_bound) {
+    const double g = gamma ? gamma[c] : 1.0, b = beta ? beta[c] : 0.0;
+    const double var = a.n > 0 ? a.m2 / a.n : 0.0;
+    const double inv = 1.0 / sqrt(var + double(eps));
+    smean[s * C + c] = float(a.mean);
+    sinv[s * C + c] = float(inv);
+    const float sc = float(g * inv);
+    scale[s * C + c] = sc;
+    shift[s * C + c] = float(b - a.mean * double(sc));
+    if (act_bound) atomic_max_bound(act_bound, bn_act_bound(a.n, g, b, double(shift[s * C + c])));
+    if (update) {
+        const double uvar = a.n > 1 ? a.m2 / (a.n - 1) : var;
+        rmean[c] = float((1.0 - momentum) * rmean[c] + momentum * a.mean);
+        rvar[c] = float((1.0 - momentum) * rvar[c] + momentum * uvar);
+    }
+}
+
 // one workgroup per channel; segments in order (t1 first), running stats updated once per segment
 __global__ __launch_bounds__(BN_THREADS) void bn_stats_finalize(const float *__restrict__ rec, int C, int nseg,
                                                                 int ncps, int nrec, const float *gamma,
@@ -221,31 +253,46 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_finalize(const float *__r
                                                                 float *act_bound) {
     __shared__ DWelford sh[BN_THREADS / 64];
     const int c = blockIdx.x;
-    const int t = threadIdx.x;
     const float *rc = rec + size_t(c) * nrec * 3;
     for (int s = 0; s < nseg; ++s) {
-        DWelford w{0, 0, 0};
-        for (int k = t; k < ncps; k += BN_THREADS) {
-            const float *r = rc + size_t(s * ncps + k) * 3;
-            dmerge(w, DWelford{r[0], r[1], r[2]});
+        const DWelford a = bn_seg_merge(rc, s, ncps, sh);
+        if (threadIdx.x == 0)
+            bn_stats_emit(a, s, c, C, gamma, beta, eps, momentum, update, rmean, rvar, smean, sinv, scale, shift,
+                          act_bound);
+    }
+}
+
+// Synchronized BatchNorm, first half: this rank's record stat[seg][c] = {n, mean, M2} in double, bn_stats_finalize's
+// merge stopped before the coefficients.  One workgroup per channel.
+__global__ __launch_bounds__(BN_THREADS) void bn_stats_local_kernel(const float *__restrict__ rec, int C, int nseg,
+                                                                    int ncps, int nrec, double *__restrict__ stat) {
+    __shared__ DWelford sh[BN_THREADS / 64];
+    const int c = blockIdx.x;
+    const float *rc = rec + size_t(c) * nrec * 3;
+    for (int s = 0; s < nseg; ++s) {
+        const DWelford a = bn_seg_merge(rc, s, ncps, sh);
+        if (threadIdx.x == 0) {
+            double *o = stat + size_t(s * C + c) * 3;
+            o[0] = a.n, o[1] = a.mean, o[2] = a.m2;
         }
-        const DWelford a = block_dmerge(w, sh);
-        if (t == 0) {
-            const double g = gamma ? gamma[c] : 1.0, b = beta ? beta[c] : 0.0;
-            const double var = a.n > 0 ? a.m2 / a.n : 0.0;
-            const double inv = 1.0 / sqrt(var + double(eps));
-            smean[s * C + c] = float(a.mean);
-            sinv[s * C + c] = float(inv);
-            const float sc = float(g * inv);
-            scale[s * C + c] = sc;
-            shift[s * C + c] = float(b - a.mean * double(sc));
-            if (act_bound) atomic_max_bound(act_bound, bn_act_bound(a.n, g, b, double(shift[s * C + c])));
-            if (update) {
-                const double uvar = a.n > 1 ? a.m2 / (a.n - 1) : var;
-                rmean[c] = float((1.0 - momentum) * rmean[c] + momentum * a.mean);
-                rvar[c] = float((1.0 - momentum) * rvar[c] + momentum * uvar);
-            }
+    }
+}
+// Second half: the ranks' records stats[rank][seg][c] Chan-merged in rank order (every rank gets the same bits), then
+// bn_stats_finalize's arithmetic on the global statistics.  One thread per channel.
+__global__ void bn_stats_from_ranks_kernel(const double *__restrict__ stats, int nranks, int C, int nseg,
+                                           const float *gamma, const float *beta, float eps, float momentum,
+                                           int update, float *rmean, float *rvar, float *smean, float *sinv,
+                                           float *scale, float *shift, float *act_bound) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    for (int s = 0; s < nseg; ++s) {
+        DWelford a{0, 0, 0};
+        for (int r = 0; r < nranks; ++r) {
+            const double *q = stats + (size_t(r * nseg + s) * C + c) * 3;
+            dmerge(a, DWelford{q[0], q[1], q[2]});
         }
+        bn_stats_emit(a, s, c, C, gamma, beta, eps, momentum, update, rmean, rvar, smean, sinv, scale, shift,
+                      act_bound);
     }
 }
 
@@ -958,6 +1005,77 @@ __device__ __forceinline__ float bn_dy_bound(double da_bound, double n, double g
 // sum_seg gamma*invstd * (S1 - pseg * k1) -- zero but for the rounding of k1, as BatchNorm removes the mean.
 // frozen (the BatchNorm normalises with its running statistics, smean/sinv hold those): the statistics do not depend
 // on y, so k1 = k2 = 0 -- dy = gamma*invstd*dz -- and the conv-bias sum above is the true gradient scale * dbeta.
+// The two halves of bn_bwd_finalize, which the synchronized BatchNorm runs with a gather of the ranks' sums in between
+// (bn_bwd_sums_kernel / bn_bwd_from_sums_kernel).
+// The record-summing half: the sums of one segment's ncps records rs of a channel, left in a1[0], a2[0] for thread 0;
+// the caller puts a barrier before the next call.
+__device__ __forceinline__ void bn_bwd_seg_sums(const float2 *rs, int ncps, double *a1, double *a2) {
+    const int t = threadIdx.x;
+    // 4 records per thread and trip, loads issued together (long tile-record lists are latency-bound otherwise);
+    // fixed order: record k goes to accumulator (k / BN_THREADS) % 4
+    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    int k = t;
+    for (; k + 3 * BN_THREADS < ncps; k += 4 * BN_THREADS) {
+        float2 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = rs[k + u * BN_THREADS];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            s1[u] += v[u].x;
+            s2[u] += v[u].y;
+        }
+    }
+    for (int u = 0; k < ncps; k += BN_THREADS, ++u) {
+        const float2 v = rs[k];
+        s1[u] += v.x;
+        s2[u] += v.y;
+    }
+    double v1 = (s1[0] + s1[1]) + (s1[2] + s1[3]), v2 = (s2[0] + s2[1]) + (s2[2] + s2[3]);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {  // fixed-order xor tree in the wave, then the waves in order
+        v1 += __shfl_xor(v1, off);
+        v2 += __shfl_xor(v2, off);
+    }
+    if ((t & 63) == 0) {
+        a1[t >> 6] = v1;
+        a2[t >> 6] = v2;
+    }
+    __syncthreads();
+    if (t == 0) {
+        for (int k = 1; k < BN_THREADS / 64; ++k) {
+            a1[0] += a1[k];
+            a2[0] += a2[k];
+        }
+    }
+}
+// dgamma, dbeta and the conv-bias grad of one channel, accumulated over its segments.
+struct BnBwdAcc {
+    double tg = 0, tb = 0, db = 0;
+};
+// What one thread takes from segment s' sums of channel c.  g1, g2 over the n values the statistics were taken from
+// give the coefficients; l1, l2 over the nl values of this walk give dgamma, dbeta and the conv-bias sum.  They are the
+// same sums but under a synchronized BatchNorm, where g is every rank's and l this rank's; xs (xsum) is then this
+// rank's sum of xhat, which is zero only over all ranks.
+__device__ __forceinline__ void bn_bwd_seg_emit(double g1, double g2, double n, double l1, double l2, double nl,
+                                                double xs, bool xsum, int s, int c, int C, float *coef,
+                                                const float *gamma, const float *sinv, const float *smean, bool dbias,
+                                                const float *da_bound, float *dy_bound, int frozen, BnBwdAcc &acc) {
+    const float k1 = frozen ? 0.f : float(g1 / n);
+    const float k2 = frozen ? 0.f : float(g2 / n);
+    coef[(s * C + c) * 2 + 0] = k1;
+    coef[(s * C + c) * 2 + 1] = k2;
+    if (dy_bound) atomic_max_bound(dy_bound, bn_dy_bound(double(*da_bound), n, gamma ? gamma[c] : 1.0,
+                                                         smean[s * C + c], sinv[s * C + c], k1, k2));
+    acc.tb += l1;
+    acc.tg += l2;
+    if (dbias) {
+        const float mul = (gamma ? gamma[c] : 1.f) * sinv[s * C + c];
+        double v = l1 - nl * double(k1);
+        if (xsum) v -= double(k2) * xs;
+        acc.db += double(mul) * v;
+    }
+}
+
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalize(const float *__restrict__ rec, int C, int nseg,
                                                               int ncps, int nrec, int64_t pseg, float *coef,
                                                               float *dgamma, float *dbeta, const float *gamma,
@@ -967,64 +1085,62 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalize(const float *__res
     const int c = blockIdx.x;
     const int t = threadIdx.x;
     const float *rc = rec + size_t(c) * nrec * 2;
-    double tg = 0, tb = 0, db = 0;
+    BnBwdAcc acc;
     for (int s = 0; s < nseg; ++s) {
-        // 4 records per thread and trip, loads issued together (long tile-record lists are latency-bound otherwise);
-        // fixed order: record k goes to accumulator (k / BN_THREADS) % 4
-        double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-        const float2 *rs = reinterpret_cast<const float2 *>(rc) + size_t(s) * ncps;
-        int k = t;
-        for (; k + 3 * BN_THREADS < ncps; k += 4 * BN_THREADS) {
-            float2 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = rs[k + u * BN_THREADS];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                s1[u] += v[u].x;
-                s2[u] += v[u].y;
-            }
-        }
-        for (int u = 0; k < ncps; k += BN_THREADS, ++u) {
-            const float2 v = rs[k];
-            s1[u] += v.x;
-            s2[u] += v.y;
-        }
-        double v1 = (s1[0] + s1[1]) + (s1[2] + s1[3]), v2 = (s2[0] + s2[1]) + (s2[2] + s2[3]);
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {  // fixed-order xor tree in the wave, then the waves in order
-            v1 += __shfl_xor(v1, off);
-            v2 += __shfl_xor(v2, off);
-        }
-        if ((t & 63) == 0) {
-            a1[t >> 6] = v1;
-            a2[t >> 6] = v2;
-        }
-        __syncthreads();
-        if (t == 0) {
-            for (int k = 1; k < BN_THREADS / 64; ++k) {
-                a1[0] += a1[k];
-                a2[0] += a2[k];
-            }
-            const float k1 = frozen ? 0.f : float(a1[0] / double(pseg));
-            const float k2 = frozen ? 0.f : float(a2[0] / double(pseg));
-            coef[(s * C + c) * 2 + 0] = k1;
-            coef[(s * C + c) * 2 + 1] = k2;
-            if (dy_bound) atomic_max_bound(dy_bound, bn_dy_bound(double(*da_bound), double(pseg), gamma ? gamma[c] : 1.0,
-                                                                 smean[s * C + c], sinv[s * C + c], k1, k2));
-            tb += a1[0];
-            tg += a2[0];
-            if (dbias) {
-                const float mul = (gamma ? gamma[c] : 1.f) * sinv[s * C + c];
-                db += double(mul) * (a1[0] - double(pseg) * double(k1));
-            }
-        }
+        bn_bwd_seg_sums(reinterpret_cast<const float2 *>(rc) + size_t(s) * ncps, ncps, a1, a2);
+        if (t == 0)
+            bn_bwd_seg_emit(a1[0], a2[0], double(pseg), a1[0], a2[0], double(pseg), 0.0, false, s, c, C, coef, gamma,
+                            sinv, smean, dbias != nullptr, da_bound, dy_bound, frozen, acc);
         __syncthreads();
     }
     if (t == 0) {
-        if (dgamma) dgamma[c] = float(tg);
-        if (dbeta) dbeta[c] = float(tb);
-        if (dbias) dbias[c] = float(db);
+        if (dgamma) dgamma[c] = float(acc.tg);
+        if (dbeta) dbeta[c] = float(acc.tb);
+        if (dbias) dbias[c] = float(acc.db);
     }
+}
+
+// Synchronized BatchNorm backward, first half: this rank's sums[seg][c] = {sum dz, sum dz*xhat} in double.
+__global__ __launch_bounds__(BN_THREADS) void bn_bwd_sums_kernel(const float *__restrict__ rec, int C, int nseg,
+                                                                 int ncps, int nrec, double *__restrict__ sums) {
+    __shared__ double a1[BN_THREADS], a2[BN_THREADS];
+    const int c = blockIdx.x;
+    const float *rc = rec + size_t(c) * nrec * 2;
+    for (int s = 0; s < nseg; ++s) {
+        bn_bwd_seg_sums(reinterpret_cast<const float2 *>(rc) + size_t(s) * ncps, ncps, a1, a2);
+        if (threadIdx.x == 0) {
+            sums[size_t(s * C + c) * 2 + 0] = a1[0];
+            sums[size_t(s * C + c) * 2 + 1] = a2[0];
+        }
+        __syncthreads();
+    }
+}
+// Second half: the coefficients from the ranks' sums added in rank order over the global count (the ranks' forward
+// records stats[rank][seg][c] = {n, mean, M2} carry the counts); dgamma, dbeta and the conv-bias grad from this rank's
+// own sums, with this rank's sum of xhat = n_rank (mean_rank - mean) invstd.  One thread per channel.
+__global__ void bn_bwd_from_sums_kernel(const double *__restrict__ sums, const double *__restrict__ stats, int nranks,
+                                        int rank, int C, int nseg, float *coef, float *dgamma, float *dbeta,
+                                        const float *gamma, const float *sinv, float *dbias, const float *smean,
+                                        const float *da_bound, float *dy_bound) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    BnBwdAcc acc;
+    for (int s = 0; s < nseg; ++s) {
+        const auto at = [&](int r) { return size_t(r * nseg + s) * C + c; };
+        double g1 = sums[at(0) * 2], g2 = sums[at(0) * 2 + 1], n = stats[at(0) * 3];
+        for (int r = 1; r < nranks; ++r) {
+            g1 += sums[at(r) * 2];
+            g2 += sums[at(r) * 2 + 1];
+            n += stats[at(r) * 3];
+        }
+        const double nl = stats[at(rank) * 3];
+        const double xs = nl * (stats[at(rank) * 3 + 1] - double(smean[s * C + c])) * double(sinv[s * C + c]);
+        bn_bwd_seg_emit(g1, g2, n, sums[at(rank) * 2], sums[at(rank) * 2 + 1], nl, xs, nranks > 1, s, c, C, coef,
+                        gamma, sinv, smean, dbias != nullptr, da_bound, dy_bound, 0, acc);
+    }
+    if (dgamma) dgamma[c] = float(acc.tg);
+    if (dbeta) dbeta[c] = float(acc.tb);
+    if (dbias) dbias[c] = float(acc.db);
 }
 
 // dy = gamma*invstd*(dz - k1 - xhat*k2); optional per-chunk sums of dy (conv bias grad), brec[c][chunk]
@@ -1319,6 +1435,16 @@ namespace scd {
 // How an entry point's body runs (its `mode`): train, SCD_BN_BWD_FROZEN, or scd_bn_relu_through's single pass.
 enum { BN_TRAIN = 0, BN_FROZEN = 1, BN_THROUGH = 2 };
 
+// The backward of a BatchNorm synchronized over ranks, cut in two around the gather of the ranks' sums:
+//   sums_out set: the form's partial pass (or its tile records) and the record-summing half of bn_bwd_finalize, this
+//                 rank's {sum dz, sum dz*xhat} [nseg][c] in double -- scd_bn_relu_backward_sums;
+//   else:         the rest of bn_bwd_finalize from every rank's sums, then the form's apply walk -- _from_sums.
+struct BnSync {
+    double *sums_out;
+    const double *sums, *stats;  // [nranks][nseg][c][2], [nranks][nseg][c][3]
+    int nranks, rank;
+};
+
 // What every form of the BatchNorm + ReLU backward shares: the entry points' common arguments as they received them,
 // then what bn_bwd_check derives from them.
 struct BnBwd {
@@ -1340,7 +1466,9 @@ struct BnBwd {
     bool frozen = false;
     // scd_bn_relu_through: only the apply kernel runs, on SegThrough; no workspace, no records, no coefficients
     bool through = false;
-    void mode(int m) { frozen = m == BN_FROZEN, through = m == BN_THROUGH; }
+    // a synchronized BatchNorm's two calls (BnSync), or null: the whole backward in one
+    const BnSync *sync = nullptr;
+    void mode(int m, const BnSync *sy = nullptr) { frozen = m == BN_FROZEN, through = m == BN_THROUGH, sync = sy; }
 
     // the kernels' parameter block for a walk over segments of lseg pixels (or cells) in ncps chunks of `chunk`
     BnWalk walk(int64_t lseg, int chunk, int ncps) const {
@@ -1412,10 +1540,23 @@ template <class Partial, class Apply>
 static void bn_bwd_run(const BnBwd &b, const BnWalk &w, BnRecs r, Partial partial, Apply apply,
                        const float *da_bound = nullptr) {
     constexpr bool deferred = std::is_same_v<Apply, NoStep>;
-    if constexpr (!std::is_same_v<Partial, NoStep>) partial();
-    hipLaunchKernelGGL(bn_bwd_finalize, dim3(b.y.c), dim3(BN_THREADS), 0, b.s, r.rec, b.y.c, b.nseg, r.ncps, r.nrec,
-                       b.g.pseg, b.coef, b.dgamma, b.dbeta, b.gamma, b.save_invstd, deferred ? b.dbias_prev : nullptr,
-                       b.save_mean, da_bound, deferred ? b.dy_bound : nullptr, int(b.frozen));
+    const BnSync *sy = b.sync;
+    if constexpr (!std::is_same_v<Partial, NoStep>)
+        if (!sy || sy->sums_out) partial();
+    if (sy && sy->sums_out) {
+        hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(b.y.c), dim3(BN_THREADS), 0, b.s, r.rec, b.y.c, b.nseg, r.ncps,
+                           r.nrec, sy->sums_out);
+        return;
+    }
+    if (sy)
+        hipLaunchKernelGGL(bn_bwd_from_sums_kernel, dim3((b.y.c + 63) / 64), dim3(64), 0, b.s, sy->sums, sy->stats,
+                           sy->nranks, sy->rank, b.y.c, b.nseg, b.coef, b.dgamma, b.dbeta, b.gamma, b.save_invstd,
+                           deferred ? b.dbias_prev : nullptr, b.save_mean, da_bound, deferred ? b.dy_bound : nullptr);
+    else
+        hipLaunchKernelGGL(bn_bwd_finalize, dim3(b.y.c), dim3(BN_THREADS), 0, b.s, r.rec, b.y.c, b.nseg, r.ncps,
+                           r.nrec, b.g.pseg, b.coef, b.dgamma, b.dbeta, b.gamma, b.save_invstd,
+                           deferred ? b.dbias_prev : nullptr, b.save_mean, da_bound, deferred ? b.dy_bound : nullptr,
+                           int(b.frozen));
     if constexpr (!deferred) {
         apply(b.dbias_prev ? b.brec : nullptr);
         if (b.dbias_prev)
@@ -1506,11 +1647,12 @@ static void bn_backward_run_pooled(const BnBwd &b, PooledCells<T> P) {
 static int bn_relu_backward_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
                                  const float *save_invstd, const float *gamma, const float *scale, const float *shift,
                                  float *dgamma, float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
-                                 void *ws, size_t ws_bytes, scd_stream_t stream, int mode) {
+                                 void *ws, size_t ws_bytes, scd_stream_t stream, int mode,
+                                 const BnSync *sy = nullptr) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.mode(mode);
+    b.mode(mode, sy);
     SCD_TRY(bn_bwd_check("bn_relu_backward", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}}));
     const int dt = common_dtype("bn_relu_backward", {&y, &da, &dy});
     if (dt < 0) return SCD_ERR_ARG;
@@ -1538,11 +1680,13 @@ static int bn_relu_backward_head_impl(scd_nhwc_t y, const float *gout, const flo
                                       int32_t nseg, const float *save_mean, const float *save_invstd,
                                       const float *gamma, const float *scale, const float *shift, float *dgamma,
                                       float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, float *w_grad,
-                                      void *ws, size_t ws_bytes, scd_stream_t stream, int mode) {
+                                      void *ws, size_t ws_bytes, scd_stream_t stream, int mode,
+                                      const BnSync *sy = nullptr) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.mode(mode);
+    b.mode(mode, sy);
+    if (sy && !sy->sums_out) w_grad = nullptr;  // the sums call wrote it, from its partial pass
     const size_t need = w_grad ? scd_bn_head_workspace_bytes(y.n, y.h, y.w, y.c, nseg, n_out) : 0;
     SCD_TRY(bn_bwd_check("bn_relu_backward_head", b, {{&dy, "bn_bwd_head.dy", false, true}}, need, [&] {
         if (gout && w_head && n_out >= 1 && n_out <= 4 && pixels(y) < (int64_t(1) << 31)) return SCD_OK;
@@ -1597,11 +1741,11 @@ static int bn_relu_backward_pooled_impl(scd_nhwc_t y, scd_nhwc_t gy, const uint8
                                         const float *save_invstd, const float *gamma, const float *scale,
                                         const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
                                         scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream,
-                                        int mode) {
+                                        int mode, const BnSync *sy = nullptr) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.mode(mode);
+    b.mode(mode, sy);
     const auto more = [&] {
         if ((!gy.data && !gskip.data) || pixels(y) >= (int64_t(1) << 31)) {
             set_error("bn_relu_backward_pooled: neither gy nor gskip / 2^31 pixels or more");
@@ -1675,11 +1819,12 @@ static int bn_relu_backward_tiles_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg
                                        const float *save_invstd, const float *gamma, const float *scale,
                                        const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
                                        float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
-                                       size_t ws_bytes, scd_stream_t stream, int mode) {
+                                       size_t ws_bytes, scd_stream_t stream, int mode,
+                                       const BnSync *sy = nullptr) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
             as_stream(stream)};
-    b.mode(mode);
+    b.mode(mode, sy);
     SCD_TRY(bn_bwd_check("bn_relu_backward_tiles", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}},
                          0, [&] {
                              if (tile_rec && ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)
@@ -1710,11 +1855,12 @@ static int bn_relu_backward_coef_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg,
                                       const float *save_invstd, const float *gamma, const float *scale,
                                       const float *shift, const float *tile_rec, int32_t ntiles, float *coef,
                                       float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
-                                      float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream, int mode) {
+                                      float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream, int mode,
+                                      const BnSync *sy = nullptr) {
     clear_error();
     BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, scd_nhwc_t{}, dy_bound, ws,
             ws_bytes, as_stream(stream)};
-    b.mode(mode);
+    b.mode(mode, sy);
     SCD_TRY(bn_bwd_check("bn_relu_backward_coef", b, {{&da, "bn_bwd_coef.da", tile_rec != nullptr, !tile_rec}}, 0, [&] {
         if (coef && (!tile_rec || (ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)) &&
             (!dy_bound || da_bound))
@@ -1746,23 +1892,17 @@ extern "C" int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t ns
                                       dgamma, dbeta, dbias_prev, da_bound, dy_bound, ws, ws_bytes, stream, BN_TRAIN);
 }
 
-// Every form behind one descriptor (scd.h); the only way to the frozen mode.
-extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream) {
-    if (!d || (d->flags & ~uint32_t(SCD_BN_BWD_FROZEN))) {
-        clear_error();
-        set_error("bn_relu_backward_desc: null descriptor / unknown flags");
-        return SCD_ERR_ARG;
-    }
-    const int mode = (d->flags & SCD_BN_BWD_FROZEN) ? BN_FROZEN : BN_TRAIN;
+// A descriptor's form, run in `mode`; sy: one of a synchronized BatchNorm's two calls (BnSync), or null.
+static int bn_desc_run(const scd_bn_bwd_t *d, scd_stream_t stream, int mode, const BnSync *sy) {
     switch (d->form) {
         case SCD_BN_BWD_PLAIN:
             return bn_relu_backward_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
                                          d->dgamma, d->dbeta, d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes,
-                                         stream, mode);
+                                         stream, mode, sy);
         case SCD_BN_BWD_TILES:
             return bn_relu_backward_tiles_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
                                                d->tile_rec, d->ntiles, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
-                                               d->dy_bound, d->ws, d->ws_bytes, stream, mode);
+                                               d->dy_bound, d->ws, d->ws_bytes, stream, mode, sy);
         case SCD_BN_BWD_POOLED:
         case SCD_BN_BWD_POOLED2:
             if ((d->form == SCD_BN_BWD_POOLED2) != (d->skip_mode == 2)) {
@@ -1773,20 +1913,118 @@ extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t str
             return bn_relu_backward_pooled_impl(d->y, d->gy, d->idx, d->gskip, d->skip_mode,
                                                 d->form == SCD_BN_BWD_POOLED2 ? d->gskip2 : scd_nhwc_t{}, d->nseg,
                                                 d->mean, d->invstd, d->gamma, d->scale, d->shift, d->dgamma, d->dbeta,
-                                                d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes, stream, mode);
+                                                d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes, stream, mode,
+                                                sy);
         case SCD_BN_BWD_HEAD:
             return bn_relu_backward_head_impl(d->y, d->gout, d->w_head, d->n_out, d->nseg, d->mean, d->invstd,
                                               d->gamma, d->scale, d->shift, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
-                                              d->dy_bound, d->w_grad, d->ws, d->ws_bytes, stream, mode);
+                                              d->dy_bound, d->w_grad, d->ws, d->ws_bytes, stream, mode, sy);
         case SCD_BN_BWD_COEF:
             return bn_relu_backward_coef_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
                                               d->tile_rec, d->ntiles, d->coef, d->dgamma, d->dbeta, d->dbias_prev,
-                                              d->da_bound, d->dy_bound, d->ws, d->ws_bytes, stream, mode);
+                                              d->da_bound, d->dy_bound, d->ws, d->ws_bytes, stream, mode, sy);
         default:
             clear_error();
             set_error("bn_relu_backward_desc: unknown form %d", int(d->form));
             return SCD_ERR_ARG;
     }
+}
+
+// Every form behind one descriptor (scd.h); the only way to the frozen mode.
+extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream) {
+    if (!d || (d->flags & ~uint32_t(SCD_BN_BWD_FROZEN))) {
+        clear_error();
+        set_error("bn_relu_backward_desc: null descriptor / unknown flags");
+        return SCD_ERR_ARG;
+    }
+    return bn_desc_run(d, stream, (d->flags & SCD_BN_BWD_FROZEN) ? BN_FROZEN : BN_TRAIN, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// BatchNorm synchronized over ranks (scd.h): the statistics and the backward sums, each cut in two around the gather
+// ------------------------------------------------------------------------------------------------
+static int sync_refuse(const char *why) {
+    set_error("sync: %s", why);
+    return SCD_ERR_ARG;
+}
+
+extern "C" int scd_bn_stats_local(scd_nhwc_t y, const float *tile_rec, int32_t ntiles, int32_t tile_pixels,
+                                  int32_t nseg, double *stat, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    clear_error();
+    if (!stat) return sync_refuse("null stat");
+    if (y.c < 1 || nseg < 1) return sync_refuse("y.c and nseg must be positive");
+    hipStream_t s = as_stream(stream);
+    float *rec = static_cast<float *>(ws);
+    int ncps;
+    if (tile_rec) {  // scd_bn_stats_from_tiles' first launch
+        if (ntiles < 1 || tile_pixels < 1 || ntiles % nseg) return sync_refuse("tiles not divisible into segments");
+        if (!ws || ws_bytes < scd_bn_tile_stats_workspace_bytes(ntiles, y.c, nseg))
+            return sync_refuse("workspace too small (scd_bn_tile_stats_workspace_bytes)");
+        int tps, group;
+        tile_groups(ntiles, nseg, &tps, &group, &ncps);
+        hipLaunchKernelGGL(bn_tile_merge, dim3(nseg * ncps, (y.c + BN_THREADS - 1) / BN_THREADS), dim3(BN_THREADS), 0,
+                           s, tile_rec, y.c, tps, group, ncps, nseg * ncps, float(tile_pixels), rec);
+    } else {  // scd_bn_train_stats' first launch
+        if (bn_check(y, nseg) != SCD_OK) return sync_refuse(std::string(scd_last_error()).c_str());
+        if (!ws || ws_bytes < scd_bn_workspace_bytes(y.n, y.h, y.w, y.c, nseg))
+            return sync_refuse("workspace too small (scd_bn_workspace_bytes)");
+        const BnGeom g = bn_geom(y, nseg);
+        ncps = g.ncps;
+        SCD_WITH_T(y.dtype, T,
+                   hipLaunchKernelGGL(bn_stats_partial<T>, dim3(g.nrec, g.cgroups), dim3(BN_THREADS), 0, s,
+                                      view_ptr<const T>(y), y.ldc, y.c, g.pseg, g.ncps, g.chunk, g.nrec, g.qpb, rec));
+    }
+    hipLaunchKernelGGL(bn_stats_local_kernel, dim3(y.c), dim3(BN_THREADS), 0, s, rec, y.c, nseg, ncps, nseg * ncps,
+                       stat);
+    return launch_status("scd_bn_stats_local");
+}
+
+extern "C" int scd_bn_stats_from_ranks(const double *stats, int32_t nranks, int32_t c, int32_t nseg,
+                                       const float *gamma, const float *beta, float eps, float momentum,
+                                       int32_t update_running, float *running_mean, float *running_var,
+                                       float *save_mean, float *save_invstd, float *scale, float *shift,
+                                       float *act_bound, scd_stream_t stream) {
+    clear_error();
+    if (!stats) return sync_refuse("null stats");
+    if (nranks < 1 || c < 1 || nseg < 1) return sync_refuse("nranks, c and nseg must be positive");
+    if (!save_mean || !save_invstd || !scale || !shift || (update_running && (!running_mean || !running_var)))
+        return sync_refuse("null output");
+    hipLaunchKernelGGL(bn_stats_from_ranks_kernel, dim3((c + 63) / 64), dim3(64), 0, as_stream(stream), stats, nranks,
+                       c, nseg, gamma, beta, eps, momentum, update_running, running_mean, running_var, save_mean,
+                       save_invstd, scale, shift, act_bound);
+    return launch_status("scd_bn_stats_from_ranks");
+}
+
+// One of the backward's two calls: the checks of both, then the descriptor's form with sy.
+static int bn_sync_run(const scd_bn_bwd_t *d, scd_stream_t stream, const BnSync &sy) {
+    clear_error();
+    if (!d) return sync_refuse("null descriptor");
+    if (d->flags & SCD_BN_BWD_FROZEN)
+        return sync_refuse("SCD_BN_BWD_FROZEN: a BatchNorm on its running statistics has nothing to synchronize "
+                           "(scd_bn_relu_backward_desc, scd_bn_relu_through)");
+    if (d->flags) return sync_refuse("unknown flags");
+    if (d->form < SCD_BN_BWD_PLAIN || d->form > SCD_BN_BWD_COEF) return sync_refuse("unknown form");
+    if (!sy.sums_out && (!sy.sums || !sy.stats)) return sync_refuse("null sums / stats");
+    if (sy.nranks < 1 || sy.rank < 0 || sy.rank >= sy.nranks) return sync_refuse("nranks < 1 / rank not in [0, nranks)");
+    const int rc = bn_desc_run(d, stream, BN_TRAIN, &sy);
+    if (rc != SCD_OK) {  // the shared bodies name their own entry points
+        const std::string why = scd_last_error();
+        set_error("sync: %s", why.c_str());
+    }
+    return rc;
+}
+
+extern "C" int scd_bn_relu_backward_sums(const scd_bn_bwd_t *d, double *sums, scd_stream_t stream) {
+    if (!sums) {
+        clear_error();
+        return sync_refuse("null sums");
+    }
+    return bn_sync_run(d, stream, BnSync{sums, nullptr, nullptr, 1, 0});
+}
+
+extern "C" int scd_bn_relu_backward_from_sums(const scd_bn_bwd_t *d, const double *sums, const double *stats,
+                                              int32_t nranks, int32_t rank, scd_stream_t stream) {
+    return bn_sync_run(d, stream, BnSync{nullptr, sums, stats, nranks, rank});
 }
 
 // The backward through a frozen BatchNorm + ReLU with nothing to train in front of it: dy = gamma*invstd*dz in one

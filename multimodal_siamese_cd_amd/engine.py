@@ -27,8 +27,9 @@ import weakref
 from dataclasses import dataclass
 
 import torch
+import torch.distributed as dist
 
-from . import hip
+from . import hip, parallel
 from .hip import TAPS_1, TAPS_2X2, TAPS_3X3, nhwc
 
 _F32 = torch.float32
@@ -378,6 +379,44 @@ class _BNSaved:
     shift: torch.Tensor
     nseg: int
     frozen: bool = False
+    sync: '_BNSync | None' = None  # the statistics are those of every rank's batch (_bn_sync_of)
+
+
+@dataclass
+class _BNSync:
+    """A BatchNorm synchronized over the ranks of `group`: what its backward needs besides the statistics.  `stats`
+    [world][nseg * c * 3] (fp64) are the ranks' forward records {n, mean, M2}, gathered: they carry every rank's count
+    (hence the global one) and mean (hence this rank's sum of xhat, which the conv-bias grad of the deferred form
+    needs)."""
+    group: object
+    world: int
+    rank: int
+    stats: torch.Tensor | None = None
+
+    def gather(self, buf: torch.Tensor) -> torch.Tensor:
+        """buf [world][...], zero but for this rank's slot -> every rank's slots: one SUM all-reduce (exact: each
+        element has one non-zero addend), the collective both gloo and RCCL carry for device tensors."""
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
+        return buf
+
+
+def bn_sync_mark(bn) -> tuple:
+    """(synchronized?, process group) of a BatchNorm module: networks.convert_sync_batchnorm's mark, or a stock
+    torch.nn.SyncBatchNorm."""
+    if isinstance(bn, torch.nn.SyncBatchNorm):
+        return True, bn.process_group
+    return bool(getattr(bn, 'scd_sync', False)), getattr(bn, 'scd_sync_group', None)
+
+
+def _bn_sync_of(bn) -> '_BNSync | None':
+    """The synchronization of a BatchNorm that is about to take batch statistics: None unless it is marked and this
+    process is one of several ranks.  Every rank must come to the same answer at the same BatchNorm call (same marks,
+    same `.training` flags), since each answer but None issues a collective."""
+    marked, group = bn_sync_mark(bn)
+    if not marked or not parallel.is_distributed():
+        return None
+    world = dist.get_world_size(group)
+    return _BNSync(group, world, dist.get_rank(group)) if world > 1 else None
 
 
 # BatchNorm `num_batches_tracked` increments of one stage, applied in one foreach launch when the stage ends
@@ -439,7 +478,16 @@ def _bn_forward(y: torch.Tensor, bn: torch.nn.BatchNorm2d, nseg: int, training: 
         mom = bn.momentum if bn.momentum is not None else 0.1
         if update and bn.momentum is None:
             raise NotImplementedError("BatchNorm2d(momentum=None) cumulative averaging is not supported")
-        if tiles is not None:
+        sy = _bn_sync_of(bn)
+        if sy is not None:  # local record (from the tile records where the conv left them), one gather, finalize
+            sy.stats = torch.zeros((sy.world, nseg * c * 3), dtype=torch.float64, device=y.device)
+            ws = _ws(hip.bn_tile_stats_workspace_bytes(tiles[1], c, nseg) if tiles is not None else
+                     hip.bn_workspace_bytes(n, h, w, c, nseg), y)
+            hip.bn_stats_local(nhwc(y), nseg, sy.stats[sy.rank], ws, tiles)
+            sy.gather(sy.stats)
+            hip.bn_stats_from_ranks(sy.stats, sy.world, c, nseg, bn.weight, bn.bias, bn.eps, mom, update,
+                                    bn.running_mean, bn.running_var, smean, sinv, scale, shift, act_bound=bound)
+        elif tiles is not None:
             rec, ntiles, tpx = tiles
             ws = _ws(hip.bn_tile_stats_workspace_bytes(ntiles, c, nseg), y)
             hip.bn_stats_from_tiles(rec, ntiles, tpx, c, nseg, bn.weight, bn.bias, bn.eps, mom, update,
@@ -450,7 +498,7 @@ def _bn_forward(y: torch.Tensor, bn: torch.nn.BatchNorm2d, nseg: int, training: 
                                bn.running_var, smean, sinv, scale, shift, ws, act_bound=bound)
         if update:
             _NBT_PENDING.append((bn.num_batches_tracked, nseg))
-        return _traced(bn, y, _BNSaved(smean, sinv, scale, shift, nseg))
+        return _traced(bn, y, _BNSaved(smean, sinv, scale, shift, nseg, sync=sy))
     if save:
         smean, sinv, scale, shift = (_empty((nseg * c,), y) for _ in range(4))
         hip.bn_frozen_coeffs(c, nseg, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, smean, sinv, scale,
@@ -633,22 +681,25 @@ def _bn_backward(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, dy_bo
         if g.w_grad is not None:
             ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, g.n_out), y)
         hip.bn_relu_backward_head(nhwc(y), g.g, g.w2, g.n_out, st.nseg, st.smean, st.sinv, bn.weight, st.scale,
-                                  st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, g.w_grad, frozen=st.frozen)
+                                  st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, g.w_grad, frozen=st.frozen,
+                                  sync=st.sync)
     elif isinstance(g, _PooledGrad) and g.gskip2 is not None:
         hip.bn_relu_backward_pooled2(nhwc(y), nhwc(g.gy) if g.gy is not None else hip._NULL, g.idx, nhwc(g.gskip),
                                      g.skip_mode, nhwc(g.gskip2), st.nseg, st.smean, st.sinv, bn.weight, st.scale,
-                                     st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen)
+                                     st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen,
+                                     sync=st.sync)
     elif isinstance(g, _PooledGrad):
         hip.bn_relu_backward_pooled(nhwc(y), nhwc(g.gy) if g.gy is not None else hip._NULL, g.idx,
                                     nhwc(g.gskip) if g.gskip is not None else hip._NULL, g.skip_mode, st.nseg,
                                     st.smean, st.sinv, bn.weight, st.scale, st.shift, dgamma, dbeta, dbias, nhwc(dy),
-                                    ws, dy_bound, frozen=st.frozen)
+                                    ws, dy_bound, frozen=st.frozen, sync=st.sync)
     elif tiles is not None:
         hip.bn_relu_backward_tiles(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
-                                   tiles[0], tiles[1], dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen)
+                                   tiles[0], tiles[1], dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen,
+                                   sync=st.sync)
     else:
         hip.bn_relu_backward(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift, dgamma,
-                             dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen)
+                             dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen, sync=st.sync)
     return dy, dgamma, dbeta, dbias
 
 
@@ -666,7 +717,7 @@ def _bn_backward_coef(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, 
     ws = _ws(hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
     hip.bn_relu_backward_coef(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
                               tiles[0] if tiles is not None else None, tiles[1] if tiles is not None else 0, coef,
-                              dgamma, dbeta, dbias, ws, da_bound, dy_bound, frozen=st.frozen)
+                              dgamma, dbeta, dbias, ws, da_bound, dy_bound, frozen=st.frozen, sync=st.sync)
     return dgamma, dbeta, dbias, coef
 
 
@@ -1641,7 +1692,8 @@ class HeadsFn(torch.autograd.Function):
                 ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, K) if need_hw else
                          hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
                 hip.bn_relu_backward_head(nhwc(y), g, ws_, K, st.nseg, st.smean, st.sinv, bn.weight, st.scale,
-                                          st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, db, wg, frozen=st.frozen)
+                                          st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, db, wg, frozen=st.frozen,
+                                          sync=st.sync)
             dys.append(_set_bound(dy, db))
             bn_grads += [dgamma, dbeta, dbias]
             wgs.append(wg)

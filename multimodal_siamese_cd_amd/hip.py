@@ -266,7 +266,13 @@ _SIGS = {
     "scd_bn_relu_backward_desc": ([POINTER(BNBWDDESC), c_void_p], c_int),
     "scd_input_grad": ([POINTER(INPUTGRAD), c_void_p], c_int),
     "scd_input_grad_supported": ([POINTER(INPUTGRAD)], c_int),
-    "scd_bn_relu_through": ([POINTER(BNBWDDESC), c_void_p], c_int),
+    "scd_bn_stats_local": ([NHWC, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+    "scd_bn_stats_from_ranks": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float, c_float, c_int32,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+                                c_int),
+    "scd_bn_relu_backward_sums": ([POINTER(BNBWDDESC), c_void_p, c_void_p], c_int),
+    "scd_bn_relu_backward_from_sums": ([POINTER(BNBWDDESC), c_void_p, c_void_p, c_int32, c_int32, c_void_p], c_int),
+    "scd_bn_relu_through": ([POINTER(BNBWDDESC), c_void_p], c_int),  # stays last (tests/test_through_bn_abi.py)
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -873,12 +879,11 @@ def bn_frozen_coeffs(c, nseg, gamma, beta, rmean, rvar, eps, mean, invstd, scale
                                       _stream()), "scd_bn_frozen_coeffs")
 
 
-def _bn_backward_frozen(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws,
-                        dy_bound, **fields):
-    """A backward form in frozen mode (scd_bn_relu_backward_desc, SCD_BN_BWD_FROZEN): smean / sinv are
-    bn_frozen_coeffs'.  `fields`: the form's own descriptor fields (NHWC views, pointers or ints)."""
+def bn_bwd_desc(form: int, flags: int, y: NHWC, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws,
+                dy_bound, **fields) -> BNBWDDESC:
+    """scd_bn_bwd_t of a backward form.  `fields`: the form's own descriptor fields (NHWC views, pointers or ints)."""
     d = BNBWDDESC()
-    d.form, d.flags, d.y, d.nseg = form, BN_BWD_FROZEN, y, nseg
+    d.form, d.flags, d.y, d.nseg = form, flags, y, nseg
     d.mean, d.invstd, d.gamma, d.scale, d.shift = smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), \
         shift.data_ptr()
     d.dgamma, d.dbeta, d.dbias_prev = _ptr(dgamma), _ptr(dbeta), _ptr(dbias)
@@ -887,14 +892,62 @@ def _bn_backward_frozen(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shi
     d.dy_bound, d.ws, d.ws_bytes = _ptr(dy_bound), ws.data_ptr(), ws.numel()
     for k, v in fields.items():
         setattr(d, k, v)
-    _check(lib().scd_bn_relu_backward_desc(ctypes.byref(d), _stream()), "scd_bn_relu_backward_desc")
+    return d
+
+
+def bn_stats_local(y: NHWC, nseg, stat: torch.Tensor, ws, tiles=None):
+    """A synchronized BatchNorm's statistics, first half: this rank's record stat [nseg][c][3] = {n, mean, M2} (fp64)
+    from a pass over y, or from the producing conv's tile records `tiles` = (records, ntiles, pixels per tile)."""
+    rec, ntiles, tpx = tiles if tiles is not None else (None, 0, 0)
+    _check(lib().scd_bn_stats_local(y, _ptr(rec), ntiles, tpx, nseg, stat.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    _stream()), "scd_bn_stats_local")
+
+
+def bn_stats_from_ranks(stats: torch.Tensor, nranks, c, nseg, gamma, beta, eps, momentum, update, rmean, rvar, smean,
+                        sinv, scale, shift, act_bound=None):
+    """Second half: bn_train_stats' outputs from the gathered records stats [nranks][nseg][c][3] (fp64), merged in
+    rank order -- the same bits on every rank."""
+    _check(lib().scd_bn_stats_from_ranks(stats.data_ptr(), nranks, c, nseg, _ptr(gamma), _ptr(beta), eps, momentum,
+                                         int(update), _ptr(rmean), _ptr(rvar), smean.data_ptr(), sinv.data_ptr(),
+                                         scale.data_ptr(), shift.data_ptr(), _ptr(act_bound), _stream()),
+           "scd_bn_stats_from_ranks")
+
+
+def bn_relu_backward_sums(d: BNBWDDESC, sums: torch.Tensor):
+    """A synchronized BatchNorm's backward, first half: this rank's sums [nseg][c][2] (fp64) of descriptor d's form
+    (and a fused head's weight grad)."""
+    _check(lib().scd_bn_relu_backward_sums(ctypes.byref(d), sums.data_ptr(), _stream()), "scd_bn_relu_backward_sums")
+
+
+def bn_relu_backward_from_sums(d: BNBWDDESC, sums: torch.Tensor, stats: torch.Tensor, nranks: int, rank: int):
+    """Second half: the coefficients from the gathered sums [nranks][nseg][c][2] and the forward's gathered records
+    `stats`, then d's apply walk; dgamma / dbeta / dbias_prev are this rank's."""
+    _check(lib().scd_bn_relu_backward_from_sums(ctypes.byref(d), sums.data_ptr(), stats.data_ptr(), nranks, rank,
+                                                _stream()), "scd_bn_relu_backward_from_sums")
+
+
+def _bn_backward_desc(frozen: bool, sync, form: int, y: NHWC, nseg, *args, **fields):
+    """A backward form through its descriptor (arguments as bn_bwd_desc's after `flags`).
+    frozen: scd_bn_relu_backward_desc with SCD_BN_BWD_FROZEN; smean / sinv are bn_frozen_coeffs' (nothing to
+    synchronize: `sync` is ignored).
+    Otherwise the BatchNorm is synchronized over ranks: sums, one gather, from_sums.  `sync` (engine._BNSync): world,
+    rank, the forward's gathered records `stats`, and gather(buf), which fills the other ranks' slots of the zeroed
+    [world][...] buffer whose slot `rank` this rank wrote."""
+    if frozen:
+        d = bn_bwd_desc(form, BN_BWD_FROZEN, y, nseg, *args, **fields)
+        return _check(lib().scd_bn_relu_backward_desc(ctypes.byref(d), _stream()), "scd_bn_relu_backward_desc")
+    d = bn_bwd_desc(form, 0, y, nseg, *args, **fields)
+    sums = torch.zeros((sync.world, nseg * y.c * 2), dtype=torch.float64, device=sync.stats.device)
+    bn_relu_backward_sums(d, sums[sync.rank])
+    sync.gather(sums)
+    bn_relu_backward_from_sums(d, sums, sync.stats, sync.world, sync.rank)
 
 
 def bn_relu_through(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shift, dy: NHWC, dy_bound=None, **fields):
     """The backward through a frozen BatchNorm + ReLU none of whose gamma, beta and conv bias in front has a gradient
     reader (scd_bn_relu_through): dy = gamma*invstd * g*[fma(y, scale, shift) > 0] in one launch, no reduction and no
     workspace.  `form`: BN_BWD_PLAIN / POOLED / POOLED2 / HEAD; `fields`: the form's own descriptor fields, as
-    _bn_backward_frozen; smean / sinv / scale / shift are bn_frozen_coeffs'."""
+    _bn_backward_desc; smean / sinv / scale / shift are bn_frozen_coeffs'."""
     d = BNBWDDESC()
     d.form, d.flags, d.y, d.nseg = form, BN_BWD_FROZEN, y, nseg
     d.mean, d.invstd, d.gamma, d.scale, d.shift = smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), \
@@ -947,12 +1000,13 @@ def bn_relu_apply(y: NHWC, nseg, scale, shift, a: NHWC):
 
 
 def bn_relu_backward(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws,
-                     dy_bound=None, frozen=False):
+                     dy_bound=None, frozen=False, sync=None):
     """`dy_bound`: device float raised to max |dy| (SCD_MATH_H2 operand scaling of the convs reading dy).
     `frozen` (every backward form): the BatchNorm used its running statistics; smean / sinv are bn_frozen_coeffs'."""
-    if frozen:
-        return _bn_backward_frozen(BN_BWD_PLAIN, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-                                   ws, dy_bound, da=da)
+    if frozen or sync is not None:
+        return _bn_backward_desc(
+            frozen, sync, BN_BWD_PLAIN, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+            ws, dy_bound, da=da)
     _check(
         lib().scd_bn_relu_backward(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
                                    shift.data_ptr(), _ptr(dgamma), _ptr(dbeta), _ptr(dbias), dy, _ptr(dy_bound),
@@ -961,11 +1015,12 @@ def bn_relu_backward(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, 
 
 
 def bn_relu_backward_pooled(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int, nseg, smean, sinv, gamma, scale,
-                            shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, frozen=False):
+                            shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, frozen=False, sync=None):
     """bn_relu_backward of da = maxpool_bwd(gy, idx) -/+ gskip (feature_grad's operand, never materialised)."""
-    if frozen:
-        return _bn_backward_frozen(BN_BWD_POOLED, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-                                   ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode)
+    if frozen or sync is not None:
+        return _bn_backward_desc(
+            frozen, sync, BN_BWD_POOLED, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+            ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode)
     _check(
         lib().scd_bn_relu_backward_pooled(y, gy, _ptr(idx), gskip, skip_mode, nseg, smean.data_ptr(), sinv.data_ptr(),
                                           _ptr(gamma), scale.data_ptr(), shift.data_ptr(), _ptr(dgamma), _ptr(dbeta),
@@ -974,13 +1029,15 @@ def bn_relu_backward_pooled(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int,
 
 
 def bn_relu_backward_pooled2(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int, gskip2: NHWC, nseg, smean, sinv,
-                             gamma, scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, frozen=False):
+                             gamma, scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, frozen=False,
+                             sync=None):
     """bn_relu_backward_pooled with the dual-task second skip gradient (skip_mode 2: gskip2 = the semantic decoder's
     [t2; t1] skip gradient, added to the -/+ difference gradient before the pooled term)."""
-    if frozen:
-        return _bn_backward_frozen(BN_BWD_POOLED2, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias,
-                                   dy, ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode,
-                                   gskip2=gskip2)
+    if frozen or sync is not None:
+        return _bn_backward_desc(
+            frozen, sync, BN_BWD_POOLED2, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias,
+            dy, ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode,
+            gskip2=gskip2)
     _check(
         lib().scd_bn_relu_backward_pooled2(y, gy, _ptr(idx), gskip, skip_mode, gskip2, nseg, smean.data_ptr(),
                                            sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), shift.data_ptr(),
@@ -994,14 +1051,16 @@ def bn_head_workspace_bytes(n, h, w, c, nseg, n_out) -> int:
 
 
 def bn_relu_backward_head(y: NHWC, gout: torch.Tensor, w_head: torch.Tensor, n_out: int, nseg, smean, sinv, gamma,
-                          scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, w_grad=None, frozen=False):
+                          scale, shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, w_grad=None, frozen=False,
+                          sync=None):
     """bn_relu_backward of da = gout . w_head, the 1x1 head's input gradient (conv1x1_bwd's gx, never materialised);
     gout NCHW [n][n_out][h][w], w_head [n_out][C].  `w_grad` ([n_out][C]): also the head's weight grad from the same
     pass (workspace bn_head_workspace_bytes)."""
-    if frozen:
-        return _bn_backward_frozen(BN_BWD_HEAD, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-                                   ws, dy_bound, gout=gout.data_ptr(), w_head=w_head.data_ptr(), n_out=n_out,
-                                   w_grad=_ptr(w_grad))
+    if frozen or sync is not None:
+        return _bn_backward_desc(
+            frozen, sync, BN_BWD_HEAD, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+            ws, dy_bound, gout=gout.data_ptr(), w_head=w_head.data_ptr(), n_out=n_out,
+            w_grad=_ptr(w_grad))
     _check(
         lib().scd_bn_relu_backward_head(y, gout.data_ptr(), w_head.data_ptr(), n_out, nseg, smean.data_ptr(),
                                         sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), shift.data_ptr(), _ptr(dgamma),
@@ -1011,11 +1070,12 @@ def bn_relu_backward_head(y: NHWC, gout: torch.Tensor, w_head: torch.Tensor, n_o
 
 
 def bn_relu_backward_tiles(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, tile_rec, ntiles, dgamma, dbeta,
-                           dbias, dy: NHWC, ws, dy_bound=None, frozen=False):
+                           dbias, dy: NHWC, ws, dy_bound=None, frozen=False, sync=None):
     """bn_relu_backward with the partial sums from conv-epilogue tile records (conv_igemm(..., bn_bwd=...))."""
-    if frozen:
-        return _bn_backward_frozen(BN_BWD_TILES, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-                                   ws, dy_bound, da=da, tile_rec=tile_rec.data_ptr(), ntiles=ntiles)
+    if frozen or sync is not None:
+        return _bn_backward_desc(
+            frozen, sync, BN_BWD_TILES, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
+            ws, dy_bound, da=da, tile_rec=tile_rec.data_ptr(), ntiles=ntiles)
     _check(
         lib().scd_bn_relu_backward_tiles(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
                                          shift.data_ptr(), tile_rec.data_ptr(), ntiles, _ptr(dgamma), _ptr(dbeta),
@@ -1024,15 +1084,16 @@ def bn_relu_backward_tiles(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, s
 
 
 def bn_relu_backward_coef(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, tile_rec, ntiles, coef, dgamma,
-                          dbeta, dbias, ws, da_bound=None, dy_bound=None, frozen=False):
+                          dbeta, dbias, ws, da_bound=None, dy_bound=None, frozen=False, sync=None):
     """The statistics half of bn_relu_backward(_tiles): coef [nseg][C][2], dgamma, dbeta, dbias (sum dy, from the
     sums) for a consumer that forms dy itself (wgrad_plan(..., rows_bn=...)).  tile_rec None: a pass over (y, da).
     `dy_bound` (with `da_bound`, a bound of |da|): raised to a bound of |dy| from the statistics (the h2 rows bound of
     that consumer)."""
-    if frozen:
-        return _bn_backward_frozen(BN_BWD_COEF, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, None,
-                                   ws, dy_bound, da=da, tile_rec=_ptr(tile_rec), ntiles=ntiles, coef=coef.data_ptr(),
-                                   da_bound=_ptr(da_bound))
+    if frozen or sync is not None:
+        return _bn_backward_desc(
+            frozen, sync, BN_BWD_COEF, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, None,
+            ws, dy_bound, da=da, tile_rec=_ptr(tile_rec), ntiles=ntiles, coef=coef.data_ptr(),
+            da_bound=_ptr(da_bound))
     _check(
         lib().scd_bn_relu_backward_coef(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
                                         shift.data_ptr(), _ptr(tile_rec), ntiles, coef.data_ptr(), _ptr(dgamma),

@@ -5,7 +5,10 @@ full replica and its own shard of image pairs (independent synthetic generator s
 data-path collective is the gradient all-reduce that DistributedDataParallel buckets and launches as the
 stage Functions (one per encoder level, then the decoder) return their gradients.  BatchNorm statistics stay per rank (like DataParallel's
 per-replica statistics) and running statistics are broadcast from rank 0 each forward
-(`broadcast_buffers=True`, DataParallel's replica-0 semantics, torch/nn/parallel/data_parallel.py:88-90).
+(`broadcast_buffers=True`, DataParallel's replica-0 semantics, torch/nn/parallel/data_parallel.py:88-90) -- unless the
+model was converted with networks.convert_sync_batchnorm (TRAINER.SYNC_BN): a converted BatchNorm in train mode takes
+its batch statistics over the batch of all ranks, one small collective per BatchNorm call and direction
+(engine._bn_forward), and its running statistics are bit-identical on every rank.
 """
 from __future__ import annotations
 
@@ -114,7 +117,11 @@ def wrap_ddp(wrapper, device=None, bucket_cap_mb: int = 16, find_unused_paramete
     to the wrapped model, not to the process: the wrapper is marked (`exact_dataparallel`), and only a loss formed
     under `loss_scope(net)` (trainers.step_loss(cfg, out, batch, net)) runs the collective.
     BatchNorm statistics stay per rank and running statistics come from rank 0 (broadcast_buffers) in both modes,
-    as DataParallel's per-replica statistics with replica 0's buffers.
+    as DataParallel's per-replica statistics with replica 0's buffers -- unless the model was converted before it came
+    here (networks.convert_sync_batchnorm): then batch statistics are global in both modes, and with
+    exact_dataparallel=True the step equals single-device training on the global batch.  A synchronized BatchNorm
+    issues collectives inside forward and backward, so its marks, every BatchNorm's `.training` and every parameter's
+    `requires_grad` must agree across ranks.
     `single_rank`: wrap even in a one-rank process group (the RCCL / DDP bucket path on one GPU,
     tests/test_rccl_gpu.py); without it a single process keeps the reference's pass-through wrapper.
     """

@@ -60,6 +60,7 @@ def run_training(cfg, device, max_steps: int | None = None):
     net = networks.create_network(cfg)
     net.to(device)
     networks.apply_freeze_params(net, cfg)  # TRAINER.FREEZE_PARAMS, once: DDP reads the flags when it builds its buckets
+    networks.apply_sync_bn(net, cfg)  # TRAINER.SYNC_BN: batch statistics over all ranks' batches (a mark; in place)
     # TRAINER.EXACT_DATAPARALLEL: the reference's gathered-batch loss of nn.DataParallel (one loss over all ranks'
     # pairs, summed gradients) instead of DDP's mean of per-rank losses (parallel.wrap_ddp)
     net = parallel.wrap_ddp(net, device, exact_dataparallel=bool(cfg.TRAINER.get('EXACT_DATAPARALLEL', False)))

@@ -141,17 +141,62 @@ def _unwrapped(net):
     return net
 
 
+# A model's BatchNorm modules: nn.BatchNorm2d, or the nn.SyncBatchNorm that torch's own convert_sync_batchnorm puts in
+# its place (the engine reads either one's parameters, buffers and flags and never calls its forward).
+_BATCHNORMS = (nn.BatchNorm2d, nn.SyncBatchNorm)
+
+
+def _prefix_tuple(prefixes):
+    if isinstance(prefixes, str):
+        prefixes = [prefixes]
+    return None if prefixes is None else tuple(str(p) for p in prefixes)
+
+
+def convert_sync_batchnorm(net, prefixes=None, process_group=None):
+    """Mark BatchNorm2d modules as synchronized over the ranks of `process_group` (None: all ranks): all of them, or
+    those whose qualified name in the model starts with one of `prefixes` (named as freeze_batchnorm names them).  In a
+    process that is one of several ranks, a marked BatchNorm that takes batch statistics takes them over the batch of
+    all ranks, and its backward is differentiated through them (torch.nn.SyncBatchNorm's semantics, inside the engine's
+    kernels); in a single process, in eval mode or frozen (freeze_batchnorm) it runs as before.
+    In place: the modules stay nn.BatchNorm2d, parameters and buffers keep their identity, state_dict keys and
+    checkpoints do not change.  A model converted with torch.nn.SyncBatchNorm.convert_sync_batchnorm is accepted too.
+    Call it before the model is wrapped for DDP.  Each synchronized BatchNorm call issues one collective in the forward
+    and one in the backward, so the marks, every BatchNorm's `.training` and every parameter's `requires_grad` must be
+    the same on all ranks (each rank needs at least one image; the counts may differ).  Returns `net`."""
+    prefixes = _prefix_tuple(prefixes)
+    for name, mod in _unwrapped(net).named_modules():
+        if isinstance(mod, nn.BatchNorm2d) and (prefixes is None or name.startswith(prefixes)):
+            mod.scd_sync, mod.scd_sync_group = True, process_group
+    return net
+
+
+def sync_bn_setting(cfg):
+    """TRAINER.SYNC_BN (absent: False): False, True (every BatchNorm) or a list of name prefixes."""
+    v = cfg.TRAINER.get('SYNC_BN', False)
+    if v is None or isinstance(v, bool):
+        return bool(v)
+    if isinstance(v, (list, tuple)) and v and all(isinstance(p, str) for p in v):
+        return [str(p) for p in v]
+    raise ValueError(f"TRAINER.SYNC_BN must be True, False or a non-empty list of name prefixes, got {v!r}")
+
+
+def apply_sync_bn(net, cfg):
+    """convert_sync_batchnorm as TRAINER.SYNC_BN asks (nothing when it is False or absent).  Returns `net`."""
+    v = sync_bn_setting(cfg)
+    if v is False:
+        return net
+    return convert_sync_batchnorm(net, None if v is True else v)
+
+
 def freeze_batchnorm(net, prefixes=None):
     """Put BatchNorm2d modules in eval mode -- they normalise with their running statistics and leave them as they
     are, while their affine parameters and everything around them keep training (fine-tuning from a checkpoint on
     small batches): all of them, or those whose qualified name in the model (`inc.conv.conv.1`, wrappers aside)
     starts with one of `prefixes`.  `net.train()` undoes it, so a loop calls this after each `net.train()`.
     Returns `net`."""
-    if isinstance(prefixes, str):
-        prefixes = [prefixes]
-    prefixes = None if prefixes is None else tuple(str(p) for p in prefixes)
+    prefixes = _prefix_tuple(prefixes)
     for name, mod in _unwrapped(net).named_modules():
-        if isinstance(mod, nn.BatchNorm2d) and (prefixes is None or name.startswith(prefixes)):
+        if isinstance(mod, _BATCHNORMS) and (prefixes is None or name.startswith(prefixes)):
             mod.eval()
     return net
 
@@ -249,8 +294,10 @@ class _HipNet(nn.Module):
         tw.train(self.training)
         any_bn_training = False
         for name, mod in self.named_modules():  # each BatchNorm follows its own flag (freeze_batchnorm)
-            if isinstance(mod, nn.BatchNorm2d):
-                tw.get_submodule(name).training = mod.training
+            if isinstance(mod, _BATCHNORMS):  # ... and carries its synchronized mark (convert_sync_batchnorm)
+                t = tw.get_submodule(name)
+                t.training = mod.training
+                t.scd_sync, t.scd_sync_group = engine.bn_sync_mark(mod)
                 any_bn_training |= mod.training
         for k, p in self.named_parameters():
             shape, m = maps[k]
