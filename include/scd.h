@@ -858,6 +858,38 @@ int scd_loss_multi_loss_from_sums(const scd_loss_term_t *terms, int32_t n_terms,
                                   float *loss, scd_stream_t stream);
 int scd_loss_multi_bwd(const scd_loss_term_t *terms, int32_t n_terms, const uint8_t *labeled, int32_t n_samples,
                        int64_t pixels, const float *sums, const float *gloss, scd_stream_t stream);
+/* The masked trio: the same terms with a per-pixel validity mask, the fused form of criterion(logits[v], target[v]).
+ * valid: a host array of n_terms device pointers, each NULL (that term is unmasked) or n_samples * pixels bytes, one
+ * per element of the term's logits; any non-zero byte means the element counts.  Every sum of a term runs over the
+ * elements that are both in its sample subset and valid, and N is their number:
+ *   counts (device int64[n_terms])  the valid selected elements per term, formed in integer arithmetic (exact at any
+ *                                   size); the mean's denominator of the pointwise kinds and the N of
+ *                                   SCD_LOSS_SOFT_DICE_BALANCED.  Row slot 4 keeps meaning "selected samples".
+ *   invalid elements                are skipped by a branch (forward) or dropped by a select (backward), never
+ *                                   multiplied by 0: NaN / Inf in logits, target or target logits there reach neither
+ *                                   the loss nor any gradient.  Their gradients are written, always, as +0.0 (glogits
+ *                                   and gtarget alike), whatever zero_unselected says; unselected samples keep the
+ *                                   zero_unselected rule.
+ *   an empty term                   (no valid selected element) contributes exactly nothing, loss 0 and gradients 0,
+ *                                   the rule of an empty sample subset.  This departs from the gather idiom, which
+ *                                   gives 1.0 for the ratio kinds and NaN for the means.
+ *   an all-ones mask                gives the loss, the rows and the gradients of the unmasked call bit for bit: same
+ *                                   grid (a function of the shape alone), same summation order, counts = selected
+ *                                   samples * pixels.
+ * A term takes 16-byte loads with one 4-byte mask word per vector when its float pointers are 16-byte and its mask
+ * pointer 4-byte aligned, and the element-by-element path otherwise.  Workspace from the masked query (it also holds
+ * the integer block counts).  Exact-DataParallel form: all-reduce `sums` (SUM, fp32) and `counts` (SUM, int64: an fp32
+ * row cannot carry an element count exactly), then scd_loss_masked_loss_from_sums re-forms coefficients and loss in
+ * place from the global rows with N = counts[t]; the bwd call then takes the global rows. */
+size_t scd_loss_masked_workspace_bytes(int32_t n_terms);
+int scd_loss_masked_fwd(const scd_loss_term_t *terms, int32_t n_terms, const uint8_t *labeled,
+                        const uint8_t *const *valid, int32_t n_samples, int64_t pixels, float *sums, int64_t *counts,
+                        float *loss, void *ws, size_t ws_bytes, scd_stream_t stream);
+int scd_loss_masked_loss_from_sums(const scd_loss_term_t *terms, int32_t n_terms, float *sums, const int64_t *counts,
+                                   float *loss, scd_stream_t stream);
+int scd_loss_masked_bwd(const scd_loss_term_t *terms, int32_t n_terms, const uint8_t *labeled,
+                        const uint8_t *const *valid, int32_t n_samples, int64_t pixels, const float *sums,
+                        const float *gloss, scd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Eval path
@@ -878,6 +910,14 @@ int scd_window_copy(scd_nhwc_t src, scd_nhwc_t dst, int32_t oy, int32_t ox, scd_
 size_t scd_threshold_counts_workspace_bytes(int64_t n, int32_t n_thr);
 int scd_threshold_counts(const float *pred, const float *truth, int64_t n, const float *thresholds, int32_t n_thr,
                          int32_t from_logits, int64_t *counts, void *ws, size_t ws_bytes, scd_stream_t stream);
+/* The same counts over the elements whose `valid` byte (n bytes, any alignment) is non-zero, with the same rounding
+ * rule: counts (device int64[2 + 2*n_thr]) = {#label, then per k: #(label & positive(k)), #positive(k)} restricted to
+ * valid elements, followed by #valid, from which TN follows on the device.  An invalid element is skipped, not
+ * compared: a NaN prediction there is not counted as positive.  Workspace from the masked query. */
+size_t scd_threshold_counts_masked_workspace_bytes(int64_t n, int32_t n_thr);
+int scd_threshold_counts_masked(const float *pred, const float *truth, const uint8_t *valid, int64_t n,
+                                const float *thresholds, int32_t n_thr, int32_t from_logits, int64_t *counts, void *ws,
+                                size_t ws_bytes, scd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Data pipeline: batched on-device augmentations (utils/augmentations.py:6-142).  Tiles are HWC fp32, one per

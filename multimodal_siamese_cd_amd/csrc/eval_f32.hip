@@ -51,37 +51,62 @@ __device__ __forceinline__ void mt_count(float p, float y, const float *thr, uin
     }
 }
 
-template <int T>
-__global__ __launch_bounds__(256) void threshold_counts_partial(const float *__restrict__ pred,
-                                                                const float *__restrict__ truth, int64_t n,
-                                                                const float *__restrict__ thr_g, int from_logits,
-                                                                unsigned long long *__restrict__ rec) {
+// MASKED: only the elements whose `valid` byte is non-zero are counted (a NaN prediction at an invalid pixel is not
+// "positive": the element is skipped, not compared), and one more counter, the last, is their number.  With
+// `valid_words` the mask pointer is 4-byte aligned: one mask word per 16-byte vector.
+template <int T, bool MASKED>
+__device__ __forceinline__ void mt_partial_body(const float *__restrict__ pred, const float *__restrict__ truth,
+                                                const uint8_t *__restrict__ valid, bool valid_words, int64_t n,
+                                                const float *__restrict__ thr_g, int from_logits,
+                                                unsigned long long *__restrict__ rec) {
     float thr[T];
 #pragma unroll
     for (int k = 0; k < T; ++k) thr[k] = thr_g[k];
-    uint32_t nt = 0, tp[T], pp[T];
+    uint32_t nt = 0, nv = 0, tp[T], pp[T];
 #pragma unroll
     for (int k = 0; k < T; ++k) tp[k] = pp[k] = 0;
     const int64_t stride = int64_t(gridDim.x) * blockDim.x;
     const int64_t n4 = n / 4;
     for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n4; i += stride) {
+        bool v0 = true, v1 = true, v2 = true, v3 = true;
+        if (MASKED) {
+            if (valid_words) {
+                const uint32_t m = reinterpret_cast<const uint32_t *>(valid)[i];
+                v0 = (m & 0xffu) != 0u;
+                v1 = (m & 0xff00u) != 0u;
+                v2 = (m & 0xff0000u) != 0u;
+                v3 = (m & 0xff000000u) != 0u;
+            } else {
+                v0 = valid[4 * i] != 0;
+                v1 = valid[4 * i + 1] != 0;
+                v2 = valid[4 * i + 2] != 0;
+                v3 = valid[4 * i + 3] != 0;
+            }
+            if (!(v0 | v1 | v2 | v3)) continue;
+            nv += uint32_t(v0) + uint32_t(v1) + uint32_t(v2) + uint32_t(v3);
+        }
         float4 p = reinterpret_cast<const float4 *>(pred)[i];
         const float4 y = reinterpret_cast<const float4 *>(truth)[i];
         if (from_logits) p = make_float4(mt_sigmoid(p.x), mt_sigmoid(p.y), mt_sigmoid(p.z), mt_sigmoid(p.w));
-        mt_count<T>(p.x, y.x, thr, nt, tp, pp);
-        mt_count<T>(p.y, y.y, thr, nt, tp, pp);
-        mt_count<T>(p.z, y.z, thr, nt, tp, pp);
-        mt_count<T>(p.w, y.w, thr, nt, tp, pp);
+        if (v0) mt_count<T>(p.x, y.x, thr, nt, tp, pp);
+        if (v1) mt_count<T>(p.y, y.y, thr, nt, tp, pp);
+        if (v2) mt_count<T>(p.z, y.z, thr, nt, tp, pp);
+        if (v3) mt_count<T>(p.w, y.w, thr, nt, tp, pp);
     }
     for (int64_t i = n4 * 4 + blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += stride) {
+        if (MASKED) {
+            if (valid[i] == 0) continue;
+            ++nv;
+        }
         const float p = from_logits ? mt_sigmoid(pred[i]) : pred[i];
         mt_count<T>(p, truth[i], thr, nt, tp, pp);
     }
     // 64-bit wave sums (DPP/permute shuffles), then the block's 4 waves through LDS
-    constexpr int NC = 1 + 2 * T;
+    constexpr int NC = 1 + 2 * T + (MASKED ? 1 : 0);
     __shared__ unsigned long long part[4][NC];
     uint32_t v[NC];
     v[0] = nt;
+    if (MASKED) v[NC - 1] = nv;
 #pragma unroll
     for (int k = 0; k < T; ++k) {
         v[1 + 2 * k] = tp[k];
@@ -98,6 +123,22 @@ __global__ __launch_bounds__(256) void threshold_counts_partial(const float *__r
     __syncthreads();
     for (int j = threadIdx.x; j < NC; j += blockDim.x)
         rec[int64_t(blockIdx.x) * NC + j] = part[0][j] + part[1][j] + part[2][j] + part[3][j];
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void threshold_counts_partial(const float *__restrict__ pred,
+                                                                const float *__restrict__ truth, int64_t n,
+                                                                const float *__restrict__ thr_g, int from_logits,
+                                                                unsigned long long *__restrict__ rec) {
+    mt_partial_body<T, false>(pred, truth, nullptr, false, n, thr_g, from_logits, rec);
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void threshold_counts_masked_partial(
+    const float *__restrict__ pred, const float *__restrict__ truth, const uint8_t *__restrict__ valid,
+    int valid_words, int64_t n, const float *__restrict__ thr_g, int from_logits,
+    unsigned long long *__restrict__ rec) {
+    mt_partial_body<T, true>(pred, truth, valid, valid_words != 0, n, thr_g, from_logits, rec);
 }
 
 // counts[j] = sum over blocks of rec[block][j] (fixed order per column; integers, so exact anyway).
@@ -124,6 +165,16 @@ static void launch_counts(const float *pred, const float *truth, int64_t n, cons
     hipLaunchKernelGGL(threshold_counts_partial<T>, dim3(blocks), dim3(256), 0, s, pred, truth, n, thr, from_logits,
                        rec);
     hipLaunchKernelGGL(threshold_counts_finalize, dim3(1), dim3(256), 0, s, rec, blocks, 1 + 2 * T, counts);
+}
+
+template <int T>
+static void launch_counts_masked(const float *pred, const float *truth, const uint8_t *valid, int64_t n,
+                                 const float *thr, int from_logits, unsigned long long *rec, int blocks,
+                                 int64_t *counts, hipStream_t s) {
+    const int words = (reinterpret_cast<uintptr_t>(valid) & 3u) == 0;
+    hipLaunchKernelGGL(threshold_counts_masked_partial<T>, dim3(blocks), dim3(256), 0, s, pred, truth, valid, words, n,
+                       thr, from_logits, rec);
+    hipLaunchKernelGGL(threshold_counts_finalize, dim3(1), dim3(256), 0, s, rec, blocks, 2 + 2 * T, counts);
 }
 
 static int mt_blocks(int64_t n) {
@@ -193,4 +244,47 @@ extern "C" int scd_threshold_counts(const float *pred, const float *truth, int64
 #undef SCD_MT_CASE
     }
     return launch_status("scd_threshold_counts");
+}
+
+extern "C" size_t scd_threshold_counts_masked_workspace_bytes(int64_t n, int32_t n_thr) {
+    if (n < 1 || n_thr < 1 || n_thr > MT_MAX) return 0;
+    return size_t(mt_blocks(n)) * size_t(2 + 2 * n_thr) * sizeof(unsigned long long);
+}
+
+extern "C" int scd_threshold_counts_masked(const float *pred, const float *truth, const uint8_t *valid, int64_t n,
+                                           const float *thresholds, int32_t n_thr, int32_t from_logits,
+                                           int64_t *counts, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    clear_error();
+    if (n_thr < 1 || n_thr > MT_MAX) {
+        set_error("threshold_counts_masked: n_thr %d outside 1..%d", n_thr, MT_MAX);
+        return SCD_ERR_ARG;
+    }
+    if (!counts) {
+        set_error("threshold_counts_masked: null counts");
+        return SCD_ERR_ARG;
+    }
+    if (!pred || !truth || !valid || !thresholds || n < 1) {
+        set_error("threshold_counts_masked: bad arguments (null pred / truth / valid / thresholds, or n < 1)");
+        return SCD_ERR_ARG;
+    }
+    if (!aligned16(pred) || !aligned16(truth)) {
+        set_error("threshold_counts_masked: pred and truth must be 16-byte aligned");
+        return SCD_ERR_ALIGN;
+    }
+    if (!ws || !aligned8(ws) || ws_bytes < scd_threshold_counts_masked_workspace_bytes(n, n_thr)) {
+        set_error("threshold_counts_masked: workspace too small or not 8-byte aligned");
+        return SCD_ERR_WORKSPACE;
+    }
+    const int blocks = mt_blocks(n);
+    auto *rec = static_cast<unsigned long long *>(ws);
+    hipStream_t s = as_stream(stream);
+    switch (n_thr) {
+#define SCD_MT_CASE(T) \
+    case T: launch_counts_masked<T>(pred, truth, valid, n, thresholds, from_logits, rec, blocks, counts, s); break;
+        SCD_MT_CASE(1) SCD_MT_CASE(2) SCD_MT_CASE(3) SCD_MT_CASE(4) SCD_MT_CASE(5) SCD_MT_CASE(6) SCD_MT_CASE(7)
+        SCD_MT_CASE(8) SCD_MT_CASE(9) SCD_MT_CASE(10) SCD_MT_CASE(11) SCD_MT_CASE(12) SCD_MT_CASE(13)
+        SCD_MT_CASE(14) SCD_MT_CASE(15) SCD_MT_CASE(16)
+#undef SCD_MT_CASE
+    }
+    return launch_status("scd_threshold_counts_masked");
 }

@@ -1933,8 +1933,12 @@ class PJaccardFn(torch.autograd.Function):
         return gl, gt
 
 
-def power_jaccard(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+def power_jaccard(logits: torch.Tensor, target: torch.Tensor, valid=None) -> torch.Tensor:
+    """valid: a per-pixel mask of the logits' shape (see multi_loss); with one the loss runs as kind 0 of the loss
+    family (the dedicated scd_pjaccard_* kernels take no mask), without one it is today's call."""
     hip.ensure_device(logits)
+    if valid is not None:
+        return single_loss(hip.LOSS_POWER_JACCARD, logits, target, valid=valid)
     return PJaccardFn.apply(logits, target)
 
 
@@ -2008,14 +2012,39 @@ def _loss_spec(spec):
     return [tuple(e) + (hip.LOSS_POWER_JACCARD, 0)[len(e) - 5:] for e in spec]
 
 
+def _term_masks(valid, n_terms: int, like: torch.Tensor):
+    """`valid` of multi_loss as a per-term list of contiguous device uint8 masks / None, or None without any mask.
+    A bool mask is reinterpreted, not copied (the kernels take any non-zero byte as "counts")."""
+    if valid is None:
+        return None
+    per_term = list(valid) if isinstance(valid, (list, tuple)) else [valid] * n_terms
+    if len(per_term) != n_terms:
+        raise ValueError(f"multi-term loss: {len(per_term)} masks for {n_terms} terms")
+    if all(v is None for v in per_term):
+        return None
+    done, out = {}, []
+    for v in per_term:
+        if v is not None and id(v) not in done:
+            if v.dtype not in (torch.bool, torch.uint8):
+                raise TypeError(f"multi-term loss: a validity mask is bool or uint8, not {v.dtype}")
+            if v.numel() != like.numel():
+                raise ValueError(f"multi-term loss: mask of {v.numel()} elements, expected {like.numel()}")
+            m = v.detach().to(device=like.device).contiguous()
+            done[id(v)] = m.view(torch.uint8) if m.dtype == torch.bool else m
+        out.append(None if v is None else done[id(v)])
+    return out
+
+
 class MultiLossFn(torch.autograd.Function):
     """sum_t coef_t * [|sel_t| > 0] * loss_kind_t(logits_t[sel_t], target_t[sel_t]) in one fused pass
     (scd_loss_multi_fwd/bwd).  spec: per term (logits index, target index, coef, select, soft, kind, sigmoid_input)
     into `tensors`; select and soft as MultiJaccardFn, kind a hip.LOSS_* value, sigmoid_input (LOSS_MSE only) takes
-    sigmoid(logits) instead of the raw logits.  No host sync: empty subsets are dropped on the device."""
+    sigmoid(logits) instead of the raw logits.  No host sync: empty subsets are dropped on the device.
+    valid (_term_masks' list, or None): per-pixel masks, the fused form of loss(logits[sel & v], target[sel & v])
+    (scd_loss_masked_fwd/bwd); None is the unmasked call, launch for launch."""
 
     @staticmethod
-    def forward(ctx, spec, labeled, *tensors):
+    def forward(ctx, spec, labeled, valid, *tensors):
         spec = _loss_spec(spec)
         ts = [t.contiguous().float() for t in tensors]
         n_samples = ts[0].shape[0]
@@ -2033,12 +2062,21 @@ class MultiLossFn(torch.autograd.Function):
                  for li, ti, c, sel, soft, kind, sig in spec]
         sums = _empty((len(spec), hip.LOSS_ROW), ts[0])
         loss = _empty((), ts[0])
-        hip.loss_multi_fwd(terms, lab, n_samples, pixels, sums, loss)
         red = _LOSS_ALLREDUCE.get()
-        if red is not None:  # exact-DataParallel: every term over the samples of all ranks
-            red(sums)
-            hip.loss_multi_loss_from_sums(terms, pixels, sums, loss)
-        ctx.spec, ctx.dims, ctx.lab = spec, (n_samples, pixels), lab
+        if valid is None:
+            hip.loss_multi_fwd(terms, lab, n_samples, pixels, sums, loss)
+            if red is not None:  # exact-DataParallel: every term over the samples of all ranks
+                red(sums)
+                hip.loss_multi_loss_from_sums(terms, pixels, sums, loss)
+        else:
+            counts = _empty((len(spec),), ts[0], torch.int64)
+            hip.loss_masked_fwd(terms, lab, valid, n_samples, pixels, sums, counts, loss)
+            if red is not None:  # the element counts travel as int64: an fp32 row cannot carry them exactly
+                red(sums)
+                red(counts)
+                hip.loss_masked_loss_from_sums(terms, sums, counts, loss)
+            ctx.counts = counts
+        ctx.spec, ctx.dims, ctx.lab, ctx.valid = spec, (n_samples, pixels), lab, valid
         ctx.save_for_backward(sums, *ts)
         return loss
 
@@ -2046,7 +2084,7 @@ class MultiLossFn(torch.autograd.Function):
     def backward(ctx, g):
         sums, *ts = ctx.saved_tensors
         n_samples, pixels = ctx.dims
-        need = ctx.needs_input_grad[2:]
+        need = ctx.needs_input_grad[3:]
         grads = [torch.empty_like(t) if need[i] else None for i, t in enumerate(ts)]
         # the writer / overlap rule of MultiJaccardFn.backward
         writers = [[] for _ in ts]
@@ -2064,21 +2102,28 @@ class MultiLossFn(torch.autograd.Function):
         terms = [dict(logits=ts[li], target=ts[ti], coef=c, select=sel, soft=soft, kind=kind, sigmoid_input=sig,
                       glogits=grads[li], gtarget=grads[ti] if soft else None, zero=zero[k])
                  for k, (li, ti, c, sel, soft, kind, sig) in enumerate(ctx.spec)]
-        hip.loss_multi_bwd(terms, ctx.lab, n_samples, pixels, sums, g.contiguous())
-        return (None, None, *grads)
+        if ctx.valid is None:
+            hip.loss_multi_bwd(terms, ctx.lab, n_samples, pixels, sums, g.contiguous())
+        else:  # invalid pixels of the selected samples get +0.0 from the kernel: the buffers above are uninitialised
+            hip.loss_masked_bwd(terms, ctx.lab, ctx.valid, n_samples, pixels, sums, g.contiguous())
+        return (None, None, None, *grads)
 
 
-def multi_loss(spec, labeled, *tensors) -> torch.Tensor:
+def multi_loss(spec, labeled, *tensors, valid=None) -> torch.Tensor:
+    """valid: a bool / uint8 mask of the logits' shape for every term, or a per-term list with None entries; a term
+    then runs over the elements that are both in its sample subset and valid (N = their number), gradients at invalid
+    pixels are +0.0, a term without any such element contributes nothing.  None: the unmasked kernels."""
     hip.ensure_device(tensors[0])
-    return MultiLossFn.apply(spec, labeled, *tensors)
+    return MultiLossFn.apply(spec, labeled, _term_masks(valid, len(spec), tensors[0]), *tensors)
 
 
 def single_loss(kind: int, logits: torch.Tensor, target: torch.Tensor, soft: bool = False,
-                sigmoid_input: bool = False) -> torch.Tensor:
+                sigmoid_input: bool = False, valid=None) -> torch.Tensor:
     """One criterion of the family over the whole batch (the plain `criterion(logits, y)` call).  soft: `target` holds
-    the logits of a sigmoid target, which receives a gradient."""
+    the logits of a sigmoid target, which receives a gradient.  valid: a per-pixel mask (multi_loss); the call then
+    equals the criterion on logits[valid], target[valid]."""
     if logits.numel() != target.numel():
         raise ValueError(f"loss: {logits.numel()} logits vs {target.numel()} targets")
     if not soft and target.requires_grad:
         raise NotImplementedError("loss: a target that needs a gradient must be given as its logits (soft=True)")
-    return multi_loss([(0, 1, 1.0, 0, int(soft), kind, int(sigmoid_input))], None, logits, target)
+    return multi_loss([(0, 1, 1.0, 0, int(soft), kind, int(sigmoid_input))], None, logits, target, valid=valid)

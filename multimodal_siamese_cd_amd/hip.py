@@ -266,6 +266,15 @@ _SIGS = {
     "scd_bn_relu_backward_desc": ([POINTER(BNBWDDESC), c_void_p], c_int),
     "scd_input_grad": ([POINTER(INPUTGRAD), c_void_p], c_int),
     "scd_input_grad_supported": ([POINTER(INPUTGRAD)], c_int),
+    "scd_loss_masked_workspace_bytes": ([c_int32], c_size_t),
+    "scd_loss_masked_fwd": ([c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_size_t, c_void_p], c_int),
+    "scd_loss_masked_loss_from_sums": ([c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "scd_loss_masked_bwd": ([c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p],
+                            c_int),
+    "scd_threshold_counts_masked_workspace_bytes": ([c_int64, c_int32], c_size_t),
+    "scd_threshold_counts_masked": ([c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p,
+                                     c_void_p, c_size_t, c_void_p], c_int),
     "scd_bn_stats_local": ([NHWC, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
     "scd_bn_stats_from_ranks": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float, c_float, c_int32,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -1220,6 +1229,24 @@ def threshold_counts(pred: torch.Tensor, truth: torch.Tensor, thresholds: torch.
            "scd_threshold_counts")
 
 
+def threshold_counts_masked_workspace_bytes(n: int, n_thr: int) -> int:
+    return lib().scd_threshold_counts_masked_workspace_bytes(n, n_thr)
+
+
+def threshold_counts_masked(pred: torch.Tensor, truth: torch.Tensor, valid: torch.Tensor, thresholds: torch.Tensor,
+                            from_logits: bool, counts: torch.Tensor, ws: torch.Tensor):
+    """counts (int64[2 + 2T]) = {#label, per threshold: TP, #positive} over the valid elements, then #valid."""
+    n = pred.numel()
+    if truth.numel() != n or counts.numel() != 2 + 2 * thresholds.numel() or counts.dtype != torch.int64:
+        raise ValueError("threshold_counts_masked: pred/truth sizes or counts buffer mismatch")
+    if valid.dtype != torch.uint8 or valid.numel() != n or not valid.is_contiguous():
+        raise ValueError(f"threshold_counts_masked: valid must be contiguous uint8 of {n} elements")
+    _check(lib().scd_threshold_counts_masked(pred.data_ptr(), truth.data_ptr(), valid.data_ptr(), n,
+                                             thresholds.data_ptr(), thresholds.numel(), int(from_logits),
+                                             counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+           "scd_threshold_counts_masked")
+
+
 class JTERM(ctypes.Structure):
     _fields_ = [("logits", c_void_p), ("target", c_void_p), ("glogits", c_void_p), ("gtarget", c_void_p),
                 ("coef", c_float), ("select", c_int32), ("soft_target", c_int32), ("zero_unselected", c_int32)]
@@ -1326,6 +1353,45 @@ def loss_multi_bwd(terms, labeled, n_samples: int, pixels: int, sums, gloss):
     arr = _lterms(terms)
     _check(lib().scd_loss_multi_bwd(ctypes.cast(arr, c_void_p), len(terms), _ptr(labeled), n_samples, pixels,
                                     sums.data_ptr(), _ptr(gloss), _stream()), "scd_loss_multi_bwd")
+
+
+def _valid_ptrs(terms, valid, n: int):
+    """The host array of per-term mask pointers (None entries: NULL); every mask is uint8 of n elements."""
+    if len(valid) != len(terms):
+        raise ValueError(f"masked loss: {len(valid)} masks for {len(terms)} terms")
+    for v in valid:
+        if v is not None and (v.dtype != torch.uint8 or v.numel() != n or not v.is_contiguous()):
+            raise ValueError(f"masked loss: a mask must be contiguous uint8 of {n} elements")
+    return (c_void_p * len(valid))(*[_ptr(v) for v in valid])
+
+
+def loss_masked_fwd(terms, labeled, valid, n_samples: int, pixels: int, sums, counts, loss):
+    """loss_multi_fwd over the valid elements only.  valid: per term a device uint8 mask of the logits' size or None;
+    counts: device int64 [n_terms], the valid selected elements per term."""
+    if counts.dtype != torch.int64 or counts.numel() != len(terms):
+        raise ValueError("masked loss: counts must be int64 [n_terms]")
+    ws = torch.empty(lib().scd_loss_masked_workspace_bytes(len(terms)), dtype=torch.uint8, device=sums.device)
+    arr, masks = _lterms(terms), _valid_ptrs(terms, valid, n_samples * pixels)
+    _check(lib().scd_loss_masked_fwd(ctypes.cast(arr, c_void_p), len(terms), _ptr(labeled),
+                                     ctypes.cast(masks, c_void_p), n_samples, pixels, sums.data_ptr(),
+                                     counts.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+           "scd_loss_masked_fwd")
+
+
+def loss_masked_bwd(terms, labeled, valid, n_samples: int, pixels: int, sums, gloss):
+    """terms as loss_masked_fwd plus {glogits, gtarget, zero}; invalid elements get +0.0."""
+    arr, masks = _lterms(terms), _valid_ptrs(terms, valid, n_samples * pixels)
+    _check(lib().scd_loss_masked_bwd(ctypes.cast(arr, c_void_p), len(terms), _ptr(labeled),
+                                     ctypes.cast(masks, c_void_p), n_samples, pixels, sums.data_ptr(), _ptr(gloss),
+                                     _stream()), "scd_loss_masked_bwd")
+
+
+def loss_masked_loss_from_sums(terms, sums, counts, loss):
+    """Coefficients and loss re-formed in place from (all-reduced) rows and (all-reduced) int64 element counts."""
+    arr = _lterms(terms)
+    _check(lib().scd_loss_masked_loss_from_sums(ctypes.cast(arr, c_void_p), len(terms), sums.data_ptr(),
+                                                counts.data_ptr(), loss.data_ptr(), _stream()),
+           "scd_loss_masked_loss_from_sums")
 
 
 def loss_multi_loss_from_sums(terms, pixels: int, sums, loss):

@@ -10,6 +10,12 @@
 Criteria of utils/loss_functions.py carry the kind of their fused kernel, so every recipe is one fused multi-term call
 (engine.multi_jaccard when every term is PowerJaccardLoss, engine.multi_loss otherwise); a foreign callable takes the
 reference's boolean-mask composition.
+
+A batch with a `valid` key (uint8 / bool (B, 1, H, W), non-zero = the pixel counts; DATALOADER.INCLUDE_MASKED) masks
+every term of its recipe, the MMCR consistency term on unlabelled samples included: each term runs over the pixels
+that are both in its sample subset and valid, with the semantics of `criterion(logits[v], y[v])` and no gather
+(engine.multi_loss(..., valid=)).  A masked PowerJaccard recipe runs as kind 0 of the loss family, an unmasked one
+keeps the dedicated kernels; a foreign callable takes the gather idiom.
 """
 from __future__ import annotations
 
@@ -28,24 +34,39 @@ def _all_power_jaccard(*criteria) -> bool:
     return all(c is loss_functions.power_jaccard_loss for c in criteria)
 
 
+def _gathered(criterion, valid, logits, target):
+    """The gather idiom, for a foreign callable: the criterion on the valid elements (a host sync)."""
+    if valid is None:
+        return criterion(logits, target)
+    v = valid.to(logits.device).bool()
+    return criterion(logits[v], target[v])
+
+
 def supervised_loss(criterion, logits, batch):
-    return criterion(logits, batch['y_change'])
+    valid = batch.get('valid')
+    if valid is None:
+        return criterion(logits, batch['y_change'])
+    if _fusable(criterion):
+        return criterion(logits, batch['y_change'], valid=valid)
+    return _gathered(criterion, valid, logits, batch['y_change'])
 
 
 def dualtask_loss(change_criterion, sem_criterion, outputs, batch):
     logits_change, logits_sem_t1, logits_sem_t2 = outputs
+    valid = batch.get('valid')
     if _fusable(change_criterion, sem_criterion):  # one fused pass: 0.5 L_change + 0.25 L_sem_t1 + 0.25 L_sem_t2
         tensors = (logits_change, batch['y_change'], logits_sem_t1, batch['y_sem_t1'], logits_sem_t2,
                    batch['y_sem_t2'])
-        if _all_power_jaccard(change_criterion, sem_criterion):  # the shipped configs: the dedicated kernels
+        if valid is None and _all_power_jaccard(change_criterion, sem_criterion):  # the shipped configs
             lab = torch.ones(logits_change.shape[0], dtype=torch.uint8, device=logits_change.device)
             spec = [(0, 1, 0.5, 0, 0), (2, 3, 0.25, 0, 0), (4, 5, 0.25, 0, 0)]
             return engine.multi_jaccard(spec, lab, *tensors)
         kc, ks = change_criterion.kind, sem_criterion.kind
         spec = [(0, 1, 0.5, 0, 0, kc, 0), (2, 3, 0.25, 0, 0, ks, 0), (4, 5, 0.25, 0, 0, ks, 0)]
-        return engine.multi_loss(spec, None, *tensors)
-    change_loss = change_criterion(logits_change, batch['y_change'])
-    sem_loss = (sem_criterion(logits_sem_t1, batch['y_sem_t1']) + sem_criterion(logits_sem_t2, batch['y_sem_t2'])) / 2
+        return engine.multi_loss(spec, None, *tensors, valid=valid)
+    change_loss = _gathered(change_criterion, valid, logits_change, batch['y_change'])
+    sem_loss = (_gathered(sem_criterion, valid, logits_sem_t1, batch['y_sem_t1'])
+                + _gathered(sem_criterion, valid, logits_sem_t2, batch['y_sem_t2'])) / 2
     return (change_loss + sem_loss) / 2
 
 
@@ -53,28 +74,33 @@ def mmcr_loss(sup_criterion, cons_criterion, outputs, batch, alpha: float, cons_
     logits_fusion, logits_s1, logits_s2 = outputs
     is_labeled = batch['is_labeled'].to(logits_fusion.device)
     y = batch['y_change']
+    valid = batch.get('valid')
     l2 = cons_loss_type == 'L2'  # train_semisupervised.py:101-102: the criterion takes sigmoid(logits_s1), not logits_s1
     if _fusable(sup_criterion, cons_criterion):
         # one fused pass, subsets selected on the device: alpha/3 * (L_f + L_s1 + L_s2)[labelled]
         # + (1 - alpha) * L_cons(logits_s1 | sigmoid(logits_s1), sigmoid(logits_s2))[unlabelled]
         a = float(alpha)
-        if not l2 and _all_power_jaccard(sup_criterion, cons_criterion):  # the shipped configs: the dedicated kernels
+        if valid is None and not l2 and _all_power_jaccard(sup_criterion, cons_criterion):  # the shipped configs
             spec = [(0, 3, a / 3, 1, 0), (1, 3, a / 3, 1, 0), (2, 3, a / 3, 1, 0), (1, 2, 1 - a, 2, 1)]
             return engine.multi_jaccard(spec, is_labeled, logits_fusion, logits_s1, logits_s2, y)
         ks, kc = sup_criterion.kind, cons_criterion.kind
         spec = [(0, 3, a / 3, 1, 0, ks, 0), (1, 3, a / 3, 1, 0, ks, 0), (2, 3, a / 3, 1, 0, ks, 0),
                 (1, 2, 1 - a, 2, 1, kc, int(l2))]
-        return engine.multi_loss(spec, is_labeled, logits_fusion, logits_s1, logits_s2, y)
+        return engine.multi_loss(spec, is_labeled, logits_fusion, logits_s1, logits_s2, y, valid=valid)
     loss = None
+    if valid is not None:
+        valid = valid.to(logits_fusion.device)
     if bool(is_labeled.any()):
-        sup = (sup_criterion(logits_fusion[is_labeled], y[is_labeled])
-               + sup_criterion(logits_s1[is_labeled], y[is_labeled])
-               + sup_criterion(logits_s2[is_labeled], y[is_labeled])) / 3
+        v = None if valid is None else valid[is_labeled]
+        sup = (_gathered(sup_criterion, v, logits_fusion[is_labeled], y[is_labeled])
+               + _gathered(sup_criterion, v, logits_s1[is_labeled], y[is_labeled])
+               + _gathered(sup_criterion, v, logits_s2[is_labeled], y[is_labeled])) / 3
         loss = alpha * sup
     if not bool(is_labeled.all()):
         nl = torch.logical_not(is_labeled)
+        v = None if valid is None else valid[nl]
         first = torch.sigmoid(logits_s1[nl]) if l2 else logits_s1[nl]
-        cons = (1 - alpha) * cons_criterion(first, torch.sigmoid(logits_s2[nl]))
+        cons = (1 - alpha) * _gathered(cons_criterion, v, first, torch.sigmoid(logits_s2[nl]))
         loss = cons if loss is None else loss + cons
     return loss
 

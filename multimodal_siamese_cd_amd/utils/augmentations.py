@@ -80,13 +80,17 @@ class DeviceAugmentation:
             p.gamma = (rng.uniform(0.25, 2, n_img), rng.uniform(0.25, 2, n_t2))
         return p
 
-    def __call__(self, imgs: list, buildings: list, change: list, draws=None, rng=np.random):
+    def __call__(self, imgs: list, buildings: list, change: list, draws=None, rng=np.random, valid=None):
         """Per-item device HWC tiles -> (imgs [B, C, S, S], buildings [B, 2, S, S], change [B, 1, S, S]).
         `draws`: per-item parameters drawn earlier (the dataset draws them in __getitem__, interleaved with its own
-        draws as the reference's per-item transform is); None = draw them now from `rng`."""
+        draws as the reference's per-item transform is); None = draw them now from `rng`.
+        `valid`: per-item HW1 fp32 validity tiles (1 = the pixel counts); they take the label's crop / flip / rot90
+        (the same `params`, one more scd_augment_apply call, no draw of their own) and come back as a fourth result,
+        uint8 [B, 1, S, S].  The importance-crop weights stay the label sums."""
         if self.no_augmentations:  # Numpy2Torch only: full tiles, one item at a time in the reference
-            return (torch.stack([t.permute(2, 0, 1) for t in imgs]), torch.stack([t.permute(2, 0, 1) for t in buildings]),
-                    torch.stack([t.permute(2, 0, 1) for t in change]))
+            chw = lambda tiles: torch.stack([t.permute(2, 0, 1) for t in tiles])
+            out = (chw(imgs), chw(buildings), chw(change))
+            return out if valid is None else out + (chw(valid).to(torch.uint8),)
         S = self.crop
         if draws is None:
             draws = [self.draw(rng, t.shape[0], t.shape[1], imgs[0].shape[2], buildings[0].shape[2]) for t in change]
@@ -113,6 +117,8 @@ class DeviceAugmentation:
         out_imgs = hip.augment_apply(imgs, S, params, s1, g1)
         out_bld = hip.augment_apply(buildings, S, params, s2, g2)
         out_chg = hip.augment_apply(change, S, params)
+        if valid is not None:
+            return out_imgs, out_bld, out_chg, hip.augment_apply(valid, S, params).to(torch.uint8)
         return out_imgs, out_bld, out_chg
 
 

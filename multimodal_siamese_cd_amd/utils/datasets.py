@@ -101,6 +101,12 @@ class MultimodalCDDataset(Dataset):
       - tiles come from an offline cache with the reference's directory layout, `.npy` (H, W, C) float32 in place
         of the GeoTIFFs (rasterio is not available): <root>/<aoi>/s1/s1_<aoi>_<year>_<mm>.npy, likewise s2 and
         buildings, plus the reference's metadata.json;
+      - DATALOADER.INCLUDE_MASKED (absent = False: the reference's behaviour, no `valid` key anywhere).  When True a
+        labelled AOI's cloud / UDM-masked timestamps are kept instead of dropped (datasets.py:117), the masks are read
+        from <root>/<aoi>/masks/masks_<aoi>_<year>_<mm>.npy ((H, W) or (H, W, 1), non-zero = unusable, the sense of
+        the reference's load_mask, dataset_helpers.py:122-136; a missing file = nothing masked), and the item carries
+        `valid` = ~(mask_t1 | mask_t2), which follows the label through the augmentations into batch['valid']
+        (uint8 (B, 1, S, S)) for the masked losses and metrics;
       - __getitem__ returns the raw full tiles and the augmentation draws (made here, after this item's own
         timestamp draws, in the reference's order); `device_collate` runs the transform chain for a whole batch
         on the GPU (utils/augmentations.py).  No multiprocessing.Manager proxies (datasets.py:103-107).
@@ -124,6 +130,7 @@ class MultimodalCDDataset(Dataset):
         self.rng = np.random if rng is None else rng
         self.dataset_mode = cfg.DATALOADER.DATASET_MODE if dataset_mode is None else dataset_mode
         self.include_building_labels = bool(cfg.DATALOADER.get('INCLUDE_BUILDING_LABELS', False))
+        self.include_masked = bool(cfg.DATALOADER.get('INCLUDE_MASKED', False))
         self.no_augmentations = no_augmentations
         self.transform = augmentations.compose_transformations(cfg, no_augmentations)
         ids = {'training': 'TRAINING_IDS', 'validation': 'VALIDATION_IDS'}.get(run_type, 'TEST_IDS')
@@ -170,13 +177,25 @@ class MultimodalCDDataset(Dataset):
         b2 = self._load_building_label(aoi_id, year_t2, month_t2)
         return np.logical_and(b1 == 0, b2 == 1).astype(np.float32)
 
+    def _load_mask(self, aoi_id, year, month, height, width):
+        """(H, W, 1) bool, True = unusable (dataset_helpers.py:122-136); no file: nothing is masked."""
+        import numpy as np
+        path = self.root_path / aoi_id / 'masks' / f'masks_{aoi_id}_{year}_{month:02d}.npy'
+        if not path.exists():
+            return np.zeros((height, width, 1), dtype=bool)
+        mask = np.load(path)
+        if mask.shape not in ((height, width), (height, width, 1)):
+            raise ValueError(f'{path}: mask of shape {mask.shape} for a {height} x {width} tile')
+        return np.nan_to_num(mask).reshape(height, width, 1) != 0
+
     def __getitem__(self, index):
         import numpy as np
         aoi_id = self.aoi_ids[index]
         labeled = self.labeled[index]
         ts = self.metadata[aoi_id]
         if labeled:
-            ts = [(t['year'], t['month']) for t in ts if t['s1'] and t['s2'] and t['buildings'] and not t['masked']]
+            ts = [(t['year'], t['month']) for t in ts if t['s1'] and t['s2'] and t['buildings']
+                  and (self.include_masked or not t['masked'])]
         else:
             ts = [(t['year'], t['month']) for t in ts if t['s1'] and t['s2']]
         idx = [0, -1] if self.dataset_mode == 'first_last' else sorted(self.rng.randint(0, len(ts), size=2))
@@ -197,8 +216,13 @@ class MultimodalCDDataset(Dataset):
         draws = None
         if not self.no_augmentations:
             draws = self.transform.draw(self.rng, change.shape[0], change.shape[1], imgs.shape[2], buildings.shape[2])
-        return {'imgs': imgs, 'buildings': buildings, 'change': change, 'aug': draws, 'aoi_id': aoi_id,
+        item = {'imgs': imgs, 'buildings': buildings, 'change': change, 'aug': draws, 'aoi_id': aoi_id,
                 'year_t1': y1, 'month_t1': m1, 'year_t2': y2, 'month_t2': m2, 'is_labeled': labeled}
+        if self.include_masked:  # after the draws, and without any of its own: the RNG stream is the unmasked one
+            h, w = change.shape[0], change.shape[1]
+            masked = np.logical_or(self._load_mask(aoi_id, y1, m1, h, w), self._load_mask(aoi_id, y2, m2, h, w))
+            item['valid'] = np.logical_not(masked).astype(np.float32)
+        return item
 
     def get_index(self, aoi_id: str):
         for index, candidate in enumerate(self.aoi_ids):
@@ -221,8 +245,10 @@ def device_collate(items: list, dataset: MultimodalCDDataset, device) -> dict:
     utils/augmentations.py run on the device for the whole batch."""
     import numpy as np
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    imgs, bld, chg = dataset.transform([up(it['imgs']) for it in items], [up(it['buildings']) for it in items],
-                                       [up(it['change']) for it in items], draws=[it['aug'] for it in items])
+    valid = [up(it['valid']) for it in items] if 'valid' in items[0] else None
+    imgs, bld, chg, *rest = dataset.transform([up(it['imgs']) for it in items], [up(it['buildings']) for it in items],
+                                              [up(it['change']) for it in items], draws=[it['aug'] for it in items],
+                                              valid=valid)
     n1, n2 = len(dataset.s1_band_indices), len(dataset.s2_band_indices)
     s1_t1, s1_t2 = imgs[:, :n1], imgs[:, n1:2 * n1]
     s2_t1, s2_t2 = imgs[:, 2 * n1:2 * n1 + n2], imgs[:, 2 * n1 + n2:]
@@ -237,6 +263,8 @@ def device_collate(items: list, dataset: MultimodalCDDataset, device) -> dict:
            'is_labeled': torch.tensor([it['is_labeled'] for it in items], device=device)}
     for k in ('aoi_id', 'year_t1', 'month_t1', 'year_t2', 'month_t2'):
         out[k] = [it[k] for it in items]
+    if valid is not None:  # DATALOADER.INCLUDE_MASKED: uint8 (B, 1, S, S), non-zero = the pixel counts
+        out['valid'] = rest[0]
     if dataset.include_building_labels:
         out['y_sem_t1'] = bld[:, 0:1].contiguous()
         out['y_sem_t2'] = bld[:, 1:2].contiguous()

@@ -43,7 +43,7 @@ def model_evaluation(net, cfg, device, run_type: str, epoch: float, step: int, d
             if isinstance(logits, (tuple, list)):
                 logits = logits[0]
             gt = item['y_change'].to(device)
-            measurer.add_logits(gt, logits)
+            measurer.add_logits(gt, logits, valid=item.get('valid'))  # a `valid` key: only those pixels count
 
     f1s = measurer.compute_f1()
     precisions, recalls = measurer.precision, measurer.recall

@@ -19,6 +19,11 @@ Two registered names raise NotImplementedError:
   SoftDiceLoss      only because tests/test_config.py::test_criterion_registry pins that; `soft_dice_loss` itself is
                     built, and SoftDiceSquaredSumLoss (identical code in the reference) resolves to it.  Flipping the
                     name on is the one line marked below.
+Every criterion takes a keyword `valid=None` beside the reference's positional signature: a bool / uint8 per-pixel
+mask of the logits' shape, and the call then equals the reference criterion on `logits[valid], target[valid]` without
+the gather (engine.multi_loss; PowerJaccardLoss runs as kind 0 of the family then).  The one departure: no valid pixel
+at all gives loss 0 and zero gradients, where the gather gives 1.0 (ratio kinds) or NaN (means).
+
 Unknown names raise like the reference (`Exception('unknown loss ...')`).  The multi-class criteria and
 jaccard_like_loss / jaccard_like_balanced_loss, which the reference never registers, are not built.
 """
@@ -32,42 +37,42 @@ _NOT_BUILT = {
 }
 
 
-def power_jaccard_loss(input, target):
+def power_jaccard_loss(input, target, valid=None):
     """1 - I / (sum(p^2 + t^2) - I + 1e-6), p = sigmoid(input), reduced over the whole batch."""
-    return engine.power_jaccard(input, target)
+    return engine.power_jaccard(input, target, valid=valid)
 
 
-def soft_dice_loss(y_logit, y_true):
+def soft_dice_loss(y_logit, y_true, valid=None):
     """1 - (2 I + 1e-6) / (sum p + sum t + 1e-6)."""
-    return engine.single_loss(hip.LOSS_SOFT_DICE, y_logit, y_true)
+    return engine.single_loss(hip.LOSS_SOFT_DICE, y_logit, y_true, valid=valid)
 
 
 soft_dice_squared_sum_loss = soft_dice_loss  # identical code in the reference (its "TODO: fix this one")
 
 
-def soft_dice_loss_balanced(input, target):
+def soft_dice_loss_balanced(input, target, valid=None):
     """1 - dice(p, t) - dice(1 - p, 1 - t), both with 1e-6 in the denominator only."""
-    return engine.single_loss(hip.LOSS_SOFT_DICE_BALANCED, input, target)
+    return engine.single_loss(hip.LOSS_SOFT_DICE_BALANCED, input, target, valid=valid)
 
 
-def iou_loss(y_logit, y_true):
+def iou_loss(y_logit, y_true, valid=None):
     """1 - I / (sum(p + t) - I + 1e-6)."""
-    return engine.single_loss(hip.LOSS_IOU, y_logit, y_true)
+    return engine.single_loss(hip.LOSS_IOU, y_logit, y_true, valid=valid)
 
 
-def dice_like_loss(input, target):
+def dice_like_loss(input, target, valid=None):
     """1 - 2 I / (sum(p^2 + t^2) + 1e-6)."""
-    return engine.single_loss(hip.LOSS_DICE_LIKE, input, target)
+    return engine.single_loss(hip.LOSS_DICE_LIKE, input, target, valid=valid)
 
 
-def bce_with_logits_loss(input, target):
+def bce_with_logits_loss(input, target, valid=None):
     """nn.BCEWithLogitsLoss(): mean(max(x, 0) - x t + log1p(exp(-|x|)))."""
-    return engine.single_loss(hip.LOSS_BCE_LOGITS, input, target)
+    return engine.single_loss(hip.LOSS_BCE_LOGITS, input, target, valid=valid)
 
 
-def mse_loss(input, target):
+def mse_loss(input, target, valid=None):
     """nn.MSELoss() on the raw logits: mean((x - t)^2)."""
-    return engine.single_loss(hip.LOSS_MSE, input, target)
+    return engine.single_loss(hip.LOSS_MSE, input, target, valid=valid)
 
 
 power_jaccard_loss.kind = hip.LOSS_POWER_JACCARD

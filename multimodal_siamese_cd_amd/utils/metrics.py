@@ -8,6 +8,10 @@ utils/evaluation.py:25 folded in) and the label once.  The kernel returns exact 
 accumulation below then adds them in the reference's order (metrics.py:28-31), so the totals are bit-identical
 to the reference's for the same inputs.
 
+`add_sample` / `add_logits` take `valid=None`: a bool / uint8 mask of the prediction's shape, and only its non-zero
+pixels are counted (`scd_threshold_counts_masked`, the confusion counts of y_true[valid], y_pred[valid] without the
+gather).  The kernel also returns #valid, so TN is formed on the device: no host sync.
+
 The small functional helpers (metrics.py:62-145) operate on whole tensors as in the reference; they are not on
 the training or eval hot path.
 """
@@ -21,9 +25,10 @@ from .. import hip
 _CLAMP = 10e-05  # the reference's clamp floor (metrics.py:41, 52, 71)
 
 
-def confusion_from_counts(counts: torch.Tensor, n: int):
+def confusion_from_counts(counts: torch.Tensor, n):
     """(TP, TN, FP, FN) int64 per threshold, in the reference's naming, from scd_threshold_counts' output
-    {#label, then per threshold: #(label & positive), #positive}."""
+    {#label, then per threshold: #(label & positive), #positive}.  n: the number of elements counted (an int, or a
+    device int64 scalar: the #valid of scd_threshold_counts_masked)."""
     counts = counts.to(torch.int64)
     n_true = counts[0]
     tp = counts[1::2]
@@ -47,7 +52,8 @@ class MultiThresholdMetric(object):
         self.FP = 0
         self.FN = 0
 
-    def _counts(self, y_true: torch.Tensor, y_pred: torch.Tensor, from_logits: bool) -> torch.Tensor:
+    def _counts(self, y_true: torch.Tensor, y_pred: torch.Tensor, from_logits: bool, valid=None):
+        """The counts vector and the number of elements counted (masked: a device scalar, #valid)."""
         hip.ensure_device(y_pred)
         pred = y_pred.detach().float().contiguous()
         truth = y_true.detach().to(device=pred.device, dtype=torch.float32).contiguous()
@@ -56,17 +62,29 @@ class MultiThresholdMetric(object):
         thr = self._threshold_vec.to(pred.device)
         T = thr.numel()
         n = pred.numel()
-        parts = []
+        if valid is not None:
+            if valid.dtype not in (torch.bool, torch.uint8) or valid.numel() != n:
+                raise ValueError(f"add_sample: valid must be bool / uint8 of {n} elements")
+            valid = valid.detach().to(pred.device).contiguous()
+            valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+        parts, n_valid = [], n
         for k0 in range(0, T, hip.THRESHOLD_MAX):
             tk = thr[k0:k0 + hip.THRESHOLD_MAX].contiguous()
-            c = torch.empty(1 + 2 * tk.numel(), dtype=torch.int64, device=pred.device)
-            ws = torch.empty(hip.threshold_counts_workspace_bytes(n, tk.numel()), dtype=torch.uint8,
-                             device=pred.device)
-            hip.threshold_counts(pred, truth, tk, from_logits, c, ws)
+            if valid is None:
+                c = torch.empty(1 + 2 * tk.numel(), dtype=torch.int64, device=pred.device)
+                ws = torch.empty(hip.threshold_counts_workspace_bytes(n, tk.numel()), dtype=torch.uint8,
+                                 device=pred.device)
+                hip.threshold_counts(pred, truth, tk, from_logits, c, ws)
+            else:
+                c = torch.empty(2 + 2 * tk.numel(), dtype=torch.int64, device=pred.device)
+                ws = torch.empty(hip.threshold_counts_masked_workspace_bytes(n, tk.numel()), dtype=torch.uint8,
+                                 device=pred.device)
+                hip.threshold_counts_masked(pred, truth, valid, tk, from_logits, c, ws)
+                c, n_valid = c[:-1], c[-1]
             parts.append(c if k0 == 0 else c[1:])
-        return torch.cat(parts) if len(parts) > 1 else parts[0]
+        return (torch.cat(parts) if len(parts) > 1 else parts[0]), n_valid
 
-    def _accumulate(self, counts: torch.Tensor, n: int):
+    def _accumulate(self, counts: torch.Tensor, n):
         tp, tn, fp, fn = confusion_from_counts(counts, n)
         # metrics.py:28-31: int64 per-sample sums -> .float() -> float32 running totals
         self.TP += tp.float()
@@ -77,18 +95,18 @@ class MultiThresholdMetric(object):
             if hasattr(self, attr):
                 delattr(self, attr)
 
-    def add_sample(self, y_true: torch.Tensor, y_pred: torch.Tensor):
-        """y_pred: probabilities (metrics.py:22), on the HIP device."""
-        self._accumulate(self._counts(y_true, y_pred, False), y_pred.numel())
+    def add_sample(self, y_true: torch.Tensor, y_pred: torch.Tensor, valid=None):
+        """y_pred: probabilities (metrics.py:22), on the HIP device.  valid: only its non-zero pixels are counted."""
+        self._accumulate(*self._counts(y_true, y_pred, False, valid))
 
-    def add_logits(self, y_true: torch.Tensor, logits: torch.Tensor):
+    def add_logits(self, y_true: torch.Tensor, logits: torch.Tensor, valid=None):
         """add_sample(y_true, sigmoid(logits)) with the sigmoid fused into the counting pass (evaluation.py:25).
 
         Bit-exact against the reference except for a pixel whose probability lies within 2 fp32 ulp of a
         threshold: there the device's 1/(1+expf(-x)) and the CPU torch.sigmoid can round to neighbouring floats
         and flip that pixel's decision (tests/test_eval_path.py::test_threshold_counts_from_logits bounds the
         count difference by that band).  `add_sample` on probabilities is bit-exact everywhere."""
-        self._accumulate(self._counts(y_true, logits, True), logits.numel())
+        self._accumulate(*self._counts(y_true, logits, True, valid))
 
     @property
     def precision(self):
