@@ -1642,30 +1642,23 @@ static void bn_backward_run_pooled(const BnBwd &b, PooledCells<T> P) {
 }
 }  // namespace scd
 
-// The entry points' bodies, shared with scd_bn_relu_backward_desc and scd_bn_relu_through: `mode` is BN_TRAIN,
-// BN_FROZEN or BN_THROUGH (BnBwd::mode).
-static int bn_relu_backward_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                 const float *save_invstd, const float *gamma, const float *scale, const float *shift,
-                                 float *dgamma, float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
-                                 void *ws, size_t ws_bytes, scd_stream_t stream, int mode,
-                                 const BnSync *sy = nullptr) {
-    clear_error();
-    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
-            as_stream(stream)};
+// What every form's body shares of a descriptor, in `mode` (BN_TRAIN, BN_FROZEN or BN_THROUGH: BnBwd::mode) and with
+// one of a synchronized BatchNorm's two calls, or null.
+static BnBwd bn_bwd_of(const scd_bn_bwd_t &d, scd_stream_t stream, int mode, const BnSync *sy) {
+    BnBwd b{d.y, d.nseg, d.mean, d.invstd, d.gamma, d.scale, d.shift, d.dgamma, d.dbeta, d.dbias_prev, d.dy, d.dy_bound,
+            d.ws, d.ws_bytes, as_stream(stream)};
     b.mode(mode, sy);
-    SCD_TRY(bn_bwd_check("bn_relu_backward", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}}));
-    const int dt = common_dtype("bn_relu_backward", {&y, &da, &dy});
-    if (dt < 0) return SCD_ERR_ARG;
-    SCD_WITH_T(dt, T, bn_backward_run<T>(b, DaPlain<T>{view_ptr<const T>(da), da.ldc}));
-    return launch_status("scd_bn_relu_backward");
+    return b;
 }
 
-extern "C" int scd_bn_relu_backward(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                    const float *save_invstd, const float *gamma, const float *scale,
-                                    const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
-                                    scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
-    return bn_relu_backward_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev,
-                                 dy, dy_bound, ws, ws_bytes, stream, BN_TRAIN);
+// The forms' bodies (bn_desc_run), each reading its own fields of the descriptor.
+static int bn_relu_backward_impl(const scd_bn_bwd_t &d, scd_stream_t stream, int mode, const BnSync *sy) {
+    BnBwd b = bn_bwd_of(d, stream, mode, sy);
+    SCD_TRY(bn_bwd_check("bn_relu_backward", b, {{&d.da, "bn_bwd.da", false, true}, {&d.dy, "bn_bwd.dy", false, true}}));
+    const int dt = common_dtype("bn_relu_backward", {&d.y, &d.da, &d.dy});
+    if (dt < 0) return SCD_ERR_ARG;
+    SCD_WITH_T(dt, T, bn_backward_run<T>(b, DaPlain<T>{view_ptr<const T>(d.da), d.da.ldc}));
+    return launch_status("scd_bn_relu_backward");
 }
 
 extern "C" size_t scd_bn_head_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t nseg,
@@ -1676,25 +1669,19 @@ extern "C" size_t scd_bn_head_workspace_bytes(int32_t n, int32_t h, int32_t w, i
     return scd_bn_workspace_bytes(n, h, w, c, nseg) + size_t(n_out > 0 ? n_out : 1) * c * g.nrec * sizeof(float);
 }
 
-static int bn_relu_backward_head_impl(scd_nhwc_t y, const float *gout, const float *w_head, int32_t n_out,
-                                      int32_t nseg, const float *save_mean, const float *save_invstd,
-                                      const float *gamma, const float *scale, const float *shift, float *dgamma,
-                                      float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, float *w_grad,
-                                      void *ws, size_t ws_bytes, scd_stream_t stream, int mode,
-                                      const BnSync *sy = nullptr) {
-    clear_error();
-    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
-            as_stream(stream)};
-    b.mode(mode, sy);
-    if (sy && !sy->sums_out) w_grad = nullptr;  // the sums call wrote it, from its partial pass
-    const size_t need = w_grad ? scd_bn_head_workspace_bytes(y.n, y.h, y.w, y.c, nseg, n_out) : 0;
-    SCD_TRY(bn_bwd_check("bn_relu_backward_head", b, {{&dy, "bn_bwd_head.dy", false, true}}, need, [&] {
-        if (gout && w_head && n_out >= 1 && n_out <= 4 && pixels(y) < (int64_t(1) << 31)) return SCD_OK;
+static int bn_relu_backward_head_impl(const scd_bn_bwd_t &d, scd_stream_t stream, int mode, const BnSync *sy) {
+    const scd_nhwc_t &y = d.y;
+    const int n_out = d.n_out;
+    BnBwd b = bn_bwd_of(d, stream, mode, sy);
+    float *w_grad = sy && !sy->sums_out ? nullptr : d.w_grad;  // the sums call wrote it, from its partial pass
+    const size_t need = w_grad ? scd_bn_head_workspace_bytes(y.n, y.h, y.w, y.c, d.nseg, n_out) : 0;
+    SCD_TRY(bn_bwd_check("bn_relu_backward_head", b, {{&d.dy, "bn_bwd_head.dy", false, true}}, need, [&] {
+        if (d.gout && d.w_head && n_out >= 1 && n_out <= 4 && pixels(y) < (int64_t(1) << 31)) return SCD_OK;
         set_error("bn_relu_backward_head: null gradient or weights / n_out not in [1,4] / 2^31 pixels or more");
         return SCD_ERR_ARG;
     }));
-    const DaHead da{gout, w_head, n_out, y.c, y.h * y.w, make_fastdiv(uint32_t(y.h * y.w))};
-    const int dt = common_dtype("bn_relu_backward_head", {&y, &dy});
+    const DaHead da{d.gout, d.w_head, n_out, y.c, y.h * y.w, make_fastdiv(uint32_t(y.h * y.w))};
+    const int dt = common_dtype("bn_relu_backward_head", {&y, &d.dy});
     if (dt < 0) return SCD_ERR_ARG;
     auto run = [&](auto no) {
         constexpr int NO = decltype(no)::value;
@@ -1713,39 +1700,13 @@ static int bn_relu_backward_head_impl(scd_nhwc_t y, const float *gout, const flo
     return launch_status("scd_bn_relu_backward_head");
 }
 
-extern "C" int scd_bn_relu_backward_head(scd_nhwc_t y, const float *gout, const float *w_head, int32_t n_out,
-                                         int32_t nseg, const float *save_mean, const float *save_invstd,
-                                         const float *gamma, const float *scale, const float *shift, float *dgamma,
-                                         float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
-                                         float *w_grad, void *ws, size_t ws_bytes, scd_stream_t stream) {
-    return bn_relu_backward_head_impl(y, gout, w_head, n_out, nseg, save_mean, save_invstd, gamma, scale, shift,
-                                      dgamma, dbeta, dbias_prev, dy, dy_bound, w_grad, ws, ws_bytes, stream, BN_TRAIN);
-}
-
-extern "C" int scd_bn_relu_backward_pooled(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
-                                           int32_t skip_mode, int32_t nseg, const float *save_mean,
-                                           const float *save_invstd, const float *gamma, const float *scale,
-                                           const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
-                                           scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
-    if (skip_mode == 2) {
-        clear_error();
-        set_error("bn_relu_backward_pooled: skip_mode 2 takes a second skip gradient (scd_bn_relu_backward_pooled2)");
-        return SCD_ERR_ARG;
-    }
-    return scd_bn_relu_backward_pooled2(y, gy, idx, gskip, skip_mode, scd_nhwc_t{}, nseg, save_mean, save_invstd, gamma,
-                                        scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream);
-}
-
-static int bn_relu_backward_pooled_impl(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
-                                        int32_t skip_mode, scd_nhwc_t gskip2, int32_t nseg, const float *save_mean,
-                                        const float *save_invstd, const float *gamma, const float *scale,
-                                        const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
-                                        scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream,
-                                        int mode, const BnSync *sy = nullptr) {
-    clear_error();
-    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
-            as_stream(stream)};
-    b.mode(mode, sy);
+// SCD_BN_BWD_POOLED and _POOLED2; the former does not read gskip2.
+static int bn_relu_backward_pooled_impl(const scd_bn_bwd_t &d, scd_stream_t stream, int mode, const BnSync *sy) {
+    const scd_nhwc_t &y = d.y, &gy = d.gy, &gskip = d.gskip, &dy = d.dy;
+    const scd_nhwc_t gskip2 = d.form == SCD_BN_BWD_POOLED2 ? d.gskip2 : scd_nhwc_t{};
+    const uint8_t *idx = d.idx;
+    const int skip_mode = d.skip_mode, nseg = d.nseg;
+    BnBwd b = bn_bwd_of(d, stream, mode, sy);
     const auto more = [&] {
         if ((!gy.data && !gskip.data) || pixels(y) >= (int64_t(1) << 31)) {
             set_error("bn_relu_backward_pooled: neither gy nor gskip / 2^31 pixels or more");
@@ -1804,27 +1765,11 @@ static int bn_relu_backward_pooled_impl(scd_nhwc_t y, scd_nhwc_t gy, const uint8
     return launch_status("scd_bn_relu_backward_pooled");
 }
 
-extern "C" int scd_bn_relu_backward_pooled2(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
-                                            int32_t skip_mode, scd_nhwc_t gskip2, int32_t nseg,
-                                            const float *save_mean, const float *save_invstd, const float *gamma,
-                                            const float *scale, const float *shift, float *dgamma, float *dbeta,
-                                            float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
-                                            size_t ws_bytes, scd_stream_t stream) {
-    return bn_relu_backward_pooled_impl(y, gy, idx, gskip, skip_mode, gskip2, nseg, save_mean, save_invstd, gamma,
-                                        scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream,
-                                        BN_TRAIN);
-}
-
-static int bn_relu_backward_tiles_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                       const float *save_invstd, const float *gamma, const float *scale,
-                                       const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
-                                       float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
-                                       size_t ws_bytes, scd_stream_t stream, int mode,
-                                       const BnSync *sy = nullptr) {
-    clear_error();
-    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes,
-            as_stream(stream)};
-    b.mode(mode, sy);
+static int bn_relu_backward_tiles_impl(const scd_bn_bwd_t &d, scd_stream_t stream, int mode, const BnSync *sy) {
+    const scd_nhwc_t &y = d.y, &da = d.da, &dy = d.dy;
+    const float *tile_rec = d.tile_rec;
+    const int ntiles = d.ntiles, nseg = d.nseg;
+    BnBwd b = bn_bwd_of(d, stream, mode, sy);
     SCD_TRY(bn_bwd_check("bn_relu_backward_tiles", b, {{&da, "bn_bwd.da", false, true}, {&dy, "bn_bwd.dy", false, true}},
                          0, [&] {
                              if (tile_rec && ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)
@@ -1842,25 +1787,13 @@ static int bn_relu_backward_tiles_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg
     return launch_status("scd_bn_relu_backward_tiles");
 }
 
-extern "C" int scd_bn_relu_backward_tiles(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                          const float *save_invstd, const float *gamma, const float *scale,
-                                          const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
-                                          float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes,
-                                          scd_stream_t stream) {
-    return bn_relu_backward_tiles_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, tile_rec, ntiles,
-                                       dgamma, dbeta, dbias_prev, dy, dy_bound, ws, ws_bytes, stream, BN_TRAIN);
-}
-
-static int bn_relu_backward_coef_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
-                                      const float *save_invstd, const float *gamma, const float *scale,
-                                      const float *shift, const float *tile_rec, int32_t ntiles, float *coef,
-                                      float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
-                                      float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream, int mode,
-                                      const BnSync *sy = nullptr) {
-    clear_error();
-    BnBwd b{y, nseg, save_mean, save_invstd, gamma, scale, shift, dgamma, dbeta, dbias_prev, scd_nhwc_t{}, dy_bound, ws,
-            ws_bytes, as_stream(stream)};
-    b.mode(mode, sy);
+static int bn_relu_backward_coef_impl(const scd_bn_bwd_t &d, scd_stream_t stream, int mode, const BnSync *sy) {
+    const scd_nhwc_t &y = d.y, &da = d.da;
+    const float *tile_rec = d.tile_rec, *da_bound = d.da_bound;
+    float *coef = d.coef, *dy_bound = d.dy_bound;
+    const int ntiles = d.ntiles, nseg = d.nseg;
+    BnBwd b = bn_bwd_of(d, stream, mode, sy);
+    b.dy = scd_nhwc_t{};  // this form has none
     SCD_TRY(bn_bwd_check("bn_relu_backward_coef", b, {{&da, "bn_bwd_coef.da", tile_rec != nullptr, !tile_rec}}, 0, [&] {
         if (coef && (!tile_rec || (ntiles >= nseg && ntiles % nseg == 0 && pixels(y) % ntiles == 0)) &&
             (!dy_bound || da_bound))
@@ -1883,62 +1816,120 @@ static int bn_relu_backward_coef_impl(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg,
     return launch_status("scd_bn_relu_backward_coef");
 }
 
+// A descriptor's form, run in `mode`; sy: one of a synchronized BatchNorm's two calls (BnSync), or null.  Every entry
+// point of the backward ends here, having cleared the last error first.
+static int bn_desc_run(const scd_bn_bwd_t &d, scd_stream_t stream, int mode, const BnSync *sy) {
+    switch (d.form) {
+        case SCD_BN_BWD_PLAIN: return bn_relu_backward_impl(d, stream, mode, sy);
+        case SCD_BN_BWD_TILES: return bn_relu_backward_tiles_impl(d, stream, mode, sy);
+        case SCD_BN_BWD_POOLED:
+        case SCD_BN_BWD_POOLED2: return bn_relu_backward_pooled_impl(d, stream, mode, sy);
+        case SCD_BN_BWD_HEAD: return bn_relu_backward_head_impl(d, stream, mode, sy);
+        case SCD_BN_BWD_COEF: return bn_relu_backward_coef_impl(d, stream, mode, sy);
+        default: set_error("bn_relu_backward_desc: unknown form %d", int(d.form)); return SCD_ERR_ARG;
+    }
+}
+
+// The public descriptor entry points' own check of the pooled forms (a positional scd_bn_relu_backward_pooled2 may
+// carry skip_mode 0 / 1).
+static const char *desc_skip_mode_error(const scd_bn_bwd_t &d) {
+    const bool pooled = d.form == SCD_BN_BWD_POOLED || d.form == SCD_BN_BWD_POOLED2;
+    if (!pooled || (d.form == SCD_BN_BWD_POOLED2) == (d.skip_mode == 2)) return nullptr;
+    return "skip_mode 2 is the form SCD_BN_BWD_POOLED2, and only it";
+}
+
+// Every form behind one descriptor (scd.h): the one path to the bodies, in every mode.
+extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream) {
+    clear_error();
+    if (!d || (d->flags & ~uint32_t(SCD_BN_BWD_FROZEN))) {
+        set_error("bn_relu_backward_desc: null descriptor / unknown flags");
+        return SCD_ERR_ARG;
+    }
+    if (const char *why = desc_skip_mode_error(*d)) {
+        set_error("bn_relu_backward_desc: %s", why);
+        return SCD_ERR_ARG;
+    }
+    return bn_desc_run(*d, stream, (d->flags & SCD_BN_BWD_FROZEN) ? BN_FROZEN : BN_TRAIN, nullptr);
+}
+
+// The positional entry points: each fills a zeroed descriptor d of its form.  BN_DESC_COMMON: the fields of the
+// arguments they all take but dy, by name.
+#define BN_DESC_COMMON(d, form_)                                                                                   \
+    scd_bn_bwd_t d{};                                                                                              \
+    d.form = form_, d.y = y, d.nseg = nseg, d.mean = save_mean, d.invstd = save_invstd, d.gamma = gamma;            \
+    d.scale = scale, d.shift = shift, d.dgamma = dgamma, d.dbeta = dbeta, d.dbias_prev = dbias_prev;               \
+    d.dy_bound = dy_bound, d.ws = ws, d.ws_bytes = ws_bytes
+
+extern "C" int scd_bn_relu_backward(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                    const float *save_invstd, const float *gamma, const float *scale,
+                                    const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
+                                    scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    clear_error();
+    BN_DESC_COMMON(d, SCD_BN_BWD_PLAIN);
+    d.dy = dy, d.da = da;
+    return bn_desc_run(d, stream, BN_TRAIN, nullptr);
+}
+
+extern "C" int scd_bn_relu_backward_tiles(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
+                                          const float *save_invstd, const float *gamma, const float *scale,
+                                          const float *shift, const float *tile_rec, int32_t ntiles, float *dgamma,
+                                          float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
+                                          size_t ws_bytes, scd_stream_t stream) {
+    clear_error();
+    BN_DESC_COMMON(d, SCD_BN_BWD_TILES);
+    d.dy = dy, d.da = da, d.tile_rec = tile_rec, d.ntiles = ntiles;
+    return bn_desc_run(d, stream, BN_TRAIN, nullptr);
+}
+
+extern "C" int scd_bn_relu_backward_pooled2(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
+                                            int32_t skip_mode, scd_nhwc_t gskip2, int32_t nseg,
+                                            const float *save_mean, const float *save_invstd, const float *gamma,
+                                            const float *scale, const float *shift, float *dgamma, float *dbeta,
+                                            float *dbias_prev, scd_nhwc_t dy, float *dy_bound, void *ws,
+                                            size_t ws_bytes, scd_stream_t stream) {
+    clear_error();
+    BN_DESC_COMMON(d, SCD_BN_BWD_POOLED2);
+    d.dy = dy, d.gy = gy, d.idx = idx, d.gskip = gskip, d.skip_mode = skip_mode, d.gskip2 = gskip2;
+    return bn_desc_run(d, stream, BN_TRAIN, nullptr);
+}
+
+extern "C" int scd_bn_relu_backward_pooled(scd_nhwc_t y, scd_nhwc_t gy, const uint8_t *idx, scd_nhwc_t gskip,
+                                           int32_t skip_mode, int32_t nseg, const float *save_mean,
+                                           const float *save_invstd, const float *gamma, const float *scale,
+                                           const float *shift, float *dgamma, float *dbeta, float *dbias_prev,
+                                           scd_nhwc_t dy, float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    clear_error();
+    if (skip_mode == 2) {
+        set_error("bn_relu_backward_pooled: skip_mode 2 takes a second skip gradient (scd_bn_relu_backward_pooled2)");
+        return SCD_ERR_ARG;
+    }
+    BN_DESC_COMMON(d, SCD_BN_BWD_POOLED);
+    d.dy = dy, d.gy = gy, d.idx = idx, d.gskip = gskip, d.skip_mode = skip_mode;
+    return bn_desc_run(d, stream, BN_TRAIN, nullptr);
+}
+
+extern "C" int scd_bn_relu_backward_head(scd_nhwc_t y, const float *gout, const float *w_head, int32_t n_out,
+                                         int32_t nseg, const float *save_mean, const float *save_invstd,
+                                         const float *gamma, const float *scale, const float *shift, float *dgamma,
+                                         float *dbeta, float *dbias_prev, scd_nhwc_t dy, float *dy_bound,
+                                         float *w_grad, void *ws, size_t ws_bytes, scd_stream_t stream) {
+    clear_error();
+    BN_DESC_COMMON(d, SCD_BN_BWD_HEAD);
+    d.dy = dy, d.gout = gout, d.w_head = w_head, d.n_out = n_out, d.w_grad = w_grad;
+    return bn_desc_run(d, stream, BN_TRAIN, nullptr);
+}
+
 extern "C" int scd_bn_relu_backward_coef(scd_nhwc_t y, scd_nhwc_t da, int32_t nseg, const float *save_mean,
                                          const float *save_invstd, const float *gamma, const float *scale,
                                          const float *shift, const float *tile_rec, int32_t ntiles, float *coef,
                                          float *dgamma, float *dbeta, float *dbias_prev, const float *da_bound,
                                          float *dy_bound, void *ws, size_t ws_bytes, scd_stream_t stream) {
-    return bn_relu_backward_coef_impl(y, da, nseg, save_mean, save_invstd, gamma, scale, shift, tile_rec, ntiles, coef,
-                                      dgamma, dbeta, dbias_prev, da_bound, dy_bound, ws, ws_bytes, stream, BN_TRAIN);
+    clear_error();
+    BN_DESC_COMMON(d, SCD_BN_BWD_COEF);
+    d.da = da, d.tile_rec = tile_rec, d.ntiles = ntiles, d.coef = coef, d.da_bound = da_bound;
+    return bn_desc_run(d, stream, BN_TRAIN, nullptr);
 }
-
-// A descriptor's form, run in `mode`; sy: one of a synchronized BatchNorm's two calls (BnSync), or null.
-static int bn_desc_run(const scd_bn_bwd_t *d, scd_stream_t stream, int mode, const BnSync *sy) {
-    switch (d->form) {
-        case SCD_BN_BWD_PLAIN:
-            return bn_relu_backward_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
-                                         d->dgamma, d->dbeta, d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes,
-                                         stream, mode, sy);
-        case SCD_BN_BWD_TILES:
-            return bn_relu_backward_tiles_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
-                                               d->tile_rec, d->ntiles, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
-                                               d->dy_bound, d->ws, d->ws_bytes, stream, mode, sy);
-        case SCD_BN_BWD_POOLED:
-        case SCD_BN_BWD_POOLED2:
-            if ((d->form == SCD_BN_BWD_POOLED2) != (d->skip_mode == 2)) {
-                clear_error();
-                set_error("bn_relu_backward_desc: skip_mode 2 is the form SCD_BN_BWD_POOLED2, and only it");
-                return SCD_ERR_ARG;
-            }
-            return bn_relu_backward_pooled_impl(d->y, d->gy, d->idx, d->gskip, d->skip_mode,
-                                                d->form == SCD_BN_BWD_POOLED2 ? d->gskip2 : scd_nhwc_t{}, d->nseg,
-                                                d->mean, d->invstd, d->gamma, d->scale, d->shift, d->dgamma, d->dbeta,
-                                                d->dbias_prev, d->dy, d->dy_bound, d->ws, d->ws_bytes, stream, mode,
-                                                sy);
-        case SCD_BN_BWD_HEAD:
-            return bn_relu_backward_head_impl(d->y, d->gout, d->w_head, d->n_out, d->nseg, d->mean, d->invstd,
-                                              d->gamma, d->scale, d->shift, d->dgamma, d->dbeta, d->dbias_prev, d->dy,
-                                              d->dy_bound, d->w_grad, d->ws, d->ws_bytes, stream, mode, sy);
-        case SCD_BN_BWD_COEF:
-            return bn_relu_backward_coef_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift,
-                                              d->tile_rec, d->ntiles, d->coef, d->dgamma, d->dbeta, d->dbias_prev,
-                                              d->da_bound, d->dy_bound, d->ws, d->ws_bytes, stream, mode, sy);
-        default:
-            clear_error();
-            set_error("bn_relu_backward_desc: unknown form %d", int(d->form));
-            return SCD_ERR_ARG;
-    }
-}
-
-// Every form behind one descriptor (scd.h); the only way to the frozen mode.
-extern "C" int scd_bn_relu_backward_desc(const scd_bn_bwd_t *d, scd_stream_t stream) {
-    if (!d || (d->flags & ~uint32_t(SCD_BN_BWD_FROZEN))) {
-        clear_error();
-        set_error("bn_relu_backward_desc: null descriptor / unknown flags");
-        return SCD_ERR_ARG;
-    }
-    return bn_desc_run(d, stream, (d->flags & SCD_BN_BWD_FROZEN) ? BN_FROZEN : BN_TRAIN, nullptr);
-}
+#undef BN_DESC_COMMON
 
 // ------------------------------------------------------------------------------------------------
 // BatchNorm synchronized over ranks (scd.h): the statistics and the backward sums, each cut in two around the gather
@@ -2006,7 +1997,11 @@ static int bn_sync_run(const scd_bn_bwd_t *d, scd_stream_t stream, const BnSync 
     if (d->form < SCD_BN_BWD_PLAIN || d->form > SCD_BN_BWD_COEF) return sync_refuse("unknown form");
     if (!sy.sums_out && (!sy.sums || !sy.stats)) return sync_refuse("null sums / stats");
     if (sy.nranks < 1 || sy.rank < 0 || sy.rank >= sy.nranks) return sync_refuse("nranks < 1 / rank not in [0, nranks)");
-    const int rc = bn_desc_run(d, stream, BN_TRAIN, &sy);
+    if (const char *why = desc_skip_mode_error(*d)) {
+        set_error("sync: bn_relu_backward_desc: %s", why);
+        return SCD_ERR_ARG;
+    }
+    const int rc = bn_desc_run(*d, stream, BN_TRAIN, &sy);
     if (rc != SCD_OK) {  // the shared bodies name their own entry points
         const std::string why = scd_last_error();
         set_error("sync: %s", why.c_str());
@@ -2050,22 +2045,9 @@ extern "C" int scd_bn_relu_through(const scd_bn_bwd_t *d, scd_stream_t stream) {
         return refuse("dgamma, dbeta, dbias_prev, w_grad and coef must be null (nothing is reduced: "
                       "scd_bn_relu_backward_desc forms them)");
     if (!d->y.data || !d->dy.data) return refuse("null y.data / dy.data");
-    const bool pooled = d->form == SCD_BN_BWD_POOLED || d->form == SCD_BN_BWD_POOLED2;
-    if (pooled && (d->form == SCD_BN_BWD_POOLED2) != (d->skip_mode == 2))
-        return refuse("skip_mode 2 is the form SCD_BN_BWD_POOLED2, and only it");
-    int rc;
-    if (d->form == SCD_BN_BWD_PLAIN)
-        rc = bn_relu_backward_impl(d->y, d->da, d->nseg, d->mean, d->invstd, d->gamma, d->scale, d->shift, nullptr,
-                                   nullptr, nullptr, d->dy, d->dy_bound, nullptr, 0, stream, BN_THROUGH);
-    else if (d->form == SCD_BN_BWD_HEAD)
-        rc = bn_relu_backward_head_impl(d->y, d->gout, d->w_head, d->n_out, d->nseg, d->mean, d->invstd, d->gamma,
-                                        d->scale, d->shift, nullptr, nullptr, nullptr, d->dy, d->dy_bound, nullptr,
-                                        nullptr, 0, stream, BN_THROUGH);
-    else
-        rc = bn_relu_backward_pooled_impl(d->y, d->gy, d->idx, d->gskip, d->skip_mode,
-                                          d->form == SCD_BN_BWD_POOLED2 ? d->gskip2 : scd_nhwc_t{}, d->nseg, d->mean,
-                                          d->invstd, d->gamma, d->scale, d->shift, nullptr, nullptr, nullptr, d->dy,
-                                          d->dy_bound, nullptr, 0, stream, BN_THROUGH);
+    if (const char *why = desc_skip_mode_error(*d)) return refuse(why);
+    // the bodies read neither the workspace nor a reduced output in this mode (bn_bwd_check; the outputs are null)
+    const int rc = bn_desc_run(*d, stream, BN_THROUGH, nullptr);
     if (rc != SCD_OK) {  // the shared bodies name their own entry points
         const std::string why = scd_last_error();
         set_error("through: %s", why.c_str());

@@ -646,21 +646,34 @@ def _bn_through(st: _BNSaved, need_gamma: bool, need_beta: bool, need_bias: bool
     return st.frozen and not (need_gamma or need_beta or need_bias)
 
 
+# hip's wrapper of each backward form, in enum scd_bn_bwd_form's order.  _bn_backward looks the name up at the call and
+# does not go straight to hip.bn_backward: the frozen-parameter tests count reducing backwards by patching these names.
+_BN_WRAPPERS = ('bn_relu_backward', 'bn_relu_backward_tiles', 'bn_relu_backward_pooled', 'bn_relu_backward_pooled2',
+                'bn_relu_backward_head', 'bn_relu_backward_coef')
+
+
+def _bn_form(g, tiles=None) -> tuple:
+    """(form, the form's own fields) of a BatchNorm backward's gradient source g: a _HeadGrad, a _PooledGrad, or the
+    gradient tensor itself, with `tiles` = (records, ntiles) of its partial sums where the producing conv's epilogue
+    left them.  The fields carry scd_bn_bwd_t's names, which are also the wrappers' parameter names."""
+    if isinstance(g, _HeadGrad):
+        return hip.BN_BWD_HEAD, dict(gout=g.g, w_head=g.w2, n_out=g.n_out, w_grad=g.w_grad)
+    if isinstance(g, _PooledGrad):
+        fields = dict(gy=nhwc(g.gy), idx=g.idx, gskip=nhwc(g.gskip), skip_mode=g.skip_mode)
+        if g.gskip2 is not None:
+            return hip.BN_BWD_POOLED2, dict(fields, gskip2=nhwc(g.gskip2))
+        return hip.BN_BWD_POOLED, fields
+    if tiles is not None:
+        return hip.BN_BWD_TILES, dict(da=nhwc(g), tile_rec=tiles[0], ntiles=tiles[1])
+    return hip.BN_BWD_PLAIN, dict(da=nhwc(g))
+
+
 def _bn_backward_through(y, g, st: _BNSaved, bn, dy_bound=None):
     """dy = gamma*invstd * g*[relu'] in one launch, no reduction; g as _bn_backward's."""
     dy = torch.empty_like(y)
-    args = (nhwc(y), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift, nhwc(dy), dy_bound)
-    if isinstance(g, _HeadGrad):
-        hip.bn_relu_through(hip.BN_BWD_HEAD, *args, gout=g.g.data_ptr(), w_head=g.w2.data_ptr(), n_out=g.n_out)
-    elif isinstance(g, _PooledGrad):
-        fields = dict(gy=nhwc(g.gy) if g.gy is not None else hip._NULL, idx=hip._ptr(g.idx),
-                      gskip=nhwc(g.gskip) if g.gskip is not None else hip._NULL, skip_mode=g.skip_mode)
-        if g.gskip2 is not None:
-            hip.bn_relu_through(hip.BN_BWD_POOLED2, *args, gskip2=nhwc(g.gskip2), **fields)
-        else:
-            hip.bn_relu_through(hip.BN_BWD_POOLED, *args, **fields)
-    else:
-        hip.bn_relu_through(hip.BN_BWD_PLAIN, *args, da=nhwc(g))
+    form, fields = _bn_form(g)
+    hip.bn_relu_through(form, nhwc(y), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift, nhwc(dy), dy_bound,
+                        **fields)
     return dy
 
 
@@ -676,30 +689,14 @@ def _bn_backward(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, dy_bo
     dbeta = _empty((c,), y) if need[1] else None
     dbias = _empty((c,), y) if conv_bias_grad else None
     n, h, w, _ = y.shape
-    ws = _ws(hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
-    if isinstance(g, _HeadGrad):
-        if g.w_grad is not None:
-            ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, g.n_out), y)
-        hip.bn_relu_backward_head(nhwc(y), g.g, g.w2, g.n_out, st.nseg, st.smean, st.sinv, bn.weight, st.scale,
-                                  st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, g.w_grad, frozen=st.frozen,
-                                  sync=st.sync)
-    elif isinstance(g, _PooledGrad) and g.gskip2 is not None:
-        hip.bn_relu_backward_pooled2(nhwc(y), nhwc(g.gy) if g.gy is not None else hip._NULL, g.idx, nhwc(g.gskip),
-                                     g.skip_mode, nhwc(g.gskip2), st.nseg, st.smean, st.sinv, bn.weight, st.scale,
-                                     st.shift, dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen,
-                                     sync=st.sync)
-    elif isinstance(g, _PooledGrad):
-        hip.bn_relu_backward_pooled(nhwc(y), nhwc(g.gy) if g.gy is not None else hip._NULL, g.idx,
-                                    nhwc(g.gskip) if g.gskip is not None else hip._NULL, g.skip_mode, st.nseg,
-                                    st.smean, st.sinv, bn.weight, st.scale, st.shift, dgamma, dbeta, dbias, nhwc(dy),
-                                    ws, dy_bound, frozen=st.frozen, sync=st.sync)
-    elif tiles is not None:
-        hip.bn_relu_backward_tiles(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
-                                   tiles[0], tiles[1], dgamma, dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen,
-                                   sync=st.sync)
-    else:
-        hip.bn_relu_backward(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift, dgamma,
-                             dbeta, dbias, nhwc(dy), ws, dy_bound, frozen=st.frozen, sync=st.sync)
+    head_wgrad = isinstance(g, _HeadGrad) and g.w_grad is not None
+    ws = _ws(hip.bn_head_workspace_bytes(n, h, w, c, st.nseg, g.n_out) if head_wgrad else
+             hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
+    form, fields = _bn_form(g, tiles)
+    getattr(hip, _BN_WRAPPERS[form])(
+        y=nhwc(y), nseg=st.nseg, smean=st.smean, sinv=st.sinv, gamma=bn.weight, scale=st.scale, shift=st.shift,
+        dgamma=dgamma, dbeta=dbeta, dbias=dbias, dy=nhwc(dy), ws=ws, dy_bound=dy_bound, frozen=st.frozen, sync=st.sync,
+        **fields)
     return dy, dgamma, dbeta, dbias
 
 
@@ -715,9 +712,12 @@ def _bn_backward_coef(y, g, st: _BNSaved, bn, conv_bias_grad: bool, tiles=None, 
     coef = _empty((st.nseg * c * 2,), y)
     n, h, w, _ = y.shape
     ws = _ws(hip.bn_workspace_bytes(n, h, w, c, st.nseg), y)
-    hip.bn_relu_backward_coef(nhwc(y), nhwc(g), st.nseg, st.smean, st.sinv, bn.weight, st.scale, st.shift,
-                              tiles[0] if tiles is not None else None, tiles[1] if tiles is not None else 0, coef,
-                              dgamma, dbeta, dbias, ws, da_bound, dy_bound, frozen=st.frozen, sync=st.sync)
+    form, fields = _bn_form(g, tiles)
+    assert form in (hip.BN_BWD_PLAIN, hip.BN_BWD_TILES)  # g is the gradient tensor: da, and the records with tiles
+    hip.bn_relu_backward_coef(
+        y=nhwc(y), nseg=st.nseg, smean=st.smean, sinv=st.sinv, gamma=bn.weight, scale=st.scale, shift=st.shift,
+        coef=coef, dgamma=dgamma, dbeta=dbeta, dbias=dbias, ws=ws, da_bound=da_bound, dy_bound=dy_bound,
+        frozen=st.frozen, sync=st.sync, **{'tile_rec': None, 'ntiles': 0, **fields})
     return dgamma, dbeta, dbias, coef
 
 

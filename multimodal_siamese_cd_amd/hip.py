@@ -889,19 +889,15 @@ def bn_frozen_coeffs(c, nseg, gamma, beta, rmean, rvar, eps, mean, invstd, scale
 
 
 def bn_bwd_desc(form: int, flags: int, y: NHWC, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws,
-                dy_bound, **fields) -> BNBWDDESC:
-    """scd_bn_bwd_t of a backward form.  `fields`: the form's own descriptor fields (NHWC views, pointers or ints)."""
-    d = BNBWDDESC()
-    d.form, d.flags, d.y, d.nseg = form, flags, y, nseg
-    d.mean, d.invstd, d.gamma, d.scale, d.shift = smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), \
-        shift.data_ptr()
-    d.dgamma, d.dbeta, d.dbias_prev = _ptr(dgamma), _ptr(dbeta), _ptr(dbias)
-    if dy is not None:
-        d.dy = dy
-    d.dy_bound, d.ws, d.ws_bytes = _ptr(dy_bound), ws.data_ptr(), ws.numel()
-    for k, v in fields.items():
-        setattr(d, k, v)
-    return d
+                dy_bound, /, **fields) -> BNBWDDESC:
+    """scd_bn_bwd_t of a backward form.  dy / ws None: the form has none.  `fields`: the form's own descriptor fields
+    (NHWC views, ints, and pointers or the tensors they point into, which the caller keeps alive)."""
+    common = dict(form=form, flags=flags, y=y, nseg=nseg, mean=smean.data_ptr(), invstd=sinv.data_ptr(),
+                  gamma=_ptr(gamma), scale=scale.data_ptr(), shift=shift.data_ptr(), dgamma=_ptr(dgamma),
+                  dbeta=_ptr(dbeta), dbias_prev=_ptr(dbias), dy=_NULL if dy is None else dy, dy_bound=_ptr(dy_bound),
+                  ws=_ptr(ws), ws_bytes=0 if ws is None else ws.numel())
+    common.update((k, v.data_ptr() if isinstance(v, torch.Tensor) else v) for k, v in fields.items())
+    return BNBWDDESC(**common)
 
 
 def bn_stats_local(y: NHWC, nseg, stat: torch.Tensor, ws, tiles=None):
@@ -935,17 +931,21 @@ def bn_relu_backward_from_sums(d: BNBWDDESC, sums: torch.Tensor, stats: torch.Te
                                                 _stream()), "scd_bn_relu_backward_from_sums")
 
 
-def _bn_backward_desc(frozen: bool, sync, form: int, y: NHWC, nseg, *args, **fields):
-    """A backward form through its descriptor (arguments as bn_bwd_desc's after `flags`).
+def bn_backward(form: int, y: NHWC, nseg, *args, frozen=False, sync=None, through=False, **fields):
+    """Every BatchNorm + ReLU backward: the descriptor of `form` (arguments as bn_bwd_desc's after `flags`), run in
+    the mode the keywords name.
+    through: scd_bn_relu_through (bn_relu_through).
     frozen: scd_bn_relu_backward_desc with SCD_BN_BWD_FROZEN; smean / sinv are bn_frozen_coeffs' (nothing to
     synchronize: `sync` is ignored).
-    Otherwise the BatchNorm is synchronized over ranks: sums, one gather, from_sums.  `sync` (engine._BNSync): world,
+    sync (engine._BNSync): the BatchNorm is synchronized over ranks: sums, one gather, from_sums.  It gives world,
     rank, the forward's gathered records `stats`, and gather(buf), which fills the other ranks' slots of the zeroed
-    [world][...] buffer whose slot `rank` this rank wrote."""
-    if frozen:
-        d = bn_bwd_desc(form, BN_BWD_FROZEN, y, nseg, *args, **fields)
+    [world][...] buffer whose slot `rank` this rank wrote.
+    Otherwise scd_bn_relu_backward_desc, train mode on this rank's batch."""
+    d = bn_bwd_desc(form, BN_BWD_FROZEN if frozen or through else 0, y, nseg, *args, **fields)
+    if through:
+        return _check(lib().scd_bn_relu_through(ctypes.byref(d), _stream()), "scd_bn_relu_through")
+    if frozen or sync is None:
         return _check(lib().scd_bn_relu_backward_desc(ctypes.byref(d), _stream()), "scd_bn_relu_backward_desc")
-    d = bn_bwd_desc(form, 0, y, nseg, *args, **fields)
     sums = torch.zeros((sync.world, nseg * y.c * 2), dtype=torch.float64, device=sync.stats.device)
     bn_relu_backward_sums(d, sums[sync.rank])
     sync.gather(sums)
@@ -956,15 +956,9 @@ def bn_relu_through(form: int, y: NHWC, nseg, smean, sinv, gamma, scale, shift, 
     """The backward through a frozen BatchNorm + ReLU none of whose gamma, beta and conv bias in front has a gradient
     reader (scd_bn_relu_through): dy = gamma*invstd * g*[fma(y, scale, shift) > 0] in one launch, no reduction and no
     workspace.  `form`: BN_BWD_PLAIN / POOLED / POOLED2 / HEAD; `fields`: the form's own descriptor fields, as
-    _bn_backward_desc; smean / sinv / scale / shift are bn_frozen_coeffs'."""
-    d = BNBWDDESC()
-    d.form, d.flags, d.y, d.nseg = form, BN_BWD_FROZEN, y, nseg
-    d.mean, d.invstd, d.gamma, d.scale, d.shift = smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), \
-        shift.data_ptr()
-    d.dy, d.dy_bound = dy, _ptr(dy_bound)
-    for k, v in fields.items():
-        setattr(d, k, v)
-    _check(lib().scd_bn_relu_through(ctypes.byref(d), _stream()), "scd_bn_relu_through")
+    bn_backward's; smean / sinv / scale / shift are bn_frozen_coeffs'."""
+    bn_backward(form, y, nseg, smean, sinv, gamma, scale, shift, None, None, None, dy, None, dy_bound, through=True,
+                **fields)
 
 
 def input_grad_desc(dy: NHWC, weight: torch.Tensor, records) -> INPUTGRAD:
@@ -1012,29 +1006,15 @@ def bn_relu_backward(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, 
                      dy_bound=None, frozen=False, sync=None):
     """`dy_bound`: device float raised to max |dy| (SCD_MATH_H2 operand scaling of the convs reading dy).
     `frozen` (every backward form): the BatchNorm used its running statistics; smean / sinv are bn_frozen_coeffs'."""
-    if frozen or sync is not None:
-        return _bn_backward_desc(
-            frozen, sync, BN_BWD_PLAIN, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-            ws, dy_bound, da=da)
-    _check(
-        lib().scd_bn_relu_backward(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
-                                   shift.data_ptr(), _ptr(dgamma), _ptr(dbeta), _ptr(dbias), dy, _ptr(dy_bound),
-                                   ws.data_ptr(), ws.numel(), _stream()),
-        "scd_bn_relu_backward")
+    bn_backward(BN_BWD_PLAIN, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws, dy_bound,
+                frozen=frozen, sync=sync, da=da)
 
 
 def bn_relu_backward_pooled(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int, nseg, smean, sinv, gamma, scale,
                             shift, dgamma, dbeta, dbias, dy: NHWC, ws, dy_bound=None, frozen=False, sync=None):
     """bn_relu_backward of da = maxpool_bwd(gy, idx) -/+ gskip (feature_grad's operand, never materialised)."""
-    if frozen or sync is not None:
-        return _bn_backward_desc(
-            frozen, sync, BN_BWD_POOLED, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-            ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode)
-    _check(
-        lib().scd_bn_relu_backward_pooled(y, gy, _ptr(idx), gskip, skip_mode, nseg, smean.data_ptr(), sinv.data_ptr(),
-                                          _ptr(gamma), scale.data_ptr(), shift.data_ptr(), _ptr(dgamma), _ptr(dbeta),
-                                          _ptr(dbias), dy, _ptr(dy_bound), ws.data_ptr(), ws.numel(), _stream()),
-        "scd_bn_relu_backward_pooled")
+    bn_backward(BN_BWD_POOLED, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws, dy_bound,
+                frozen=frozen, sync=sync, gy=gy, idx=idx, gskip=gskip, skip_mode=skip_mode)
 
 
 def bn_relu_backward_pooled2(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int, gskip2: NHWC, nseg, smean, sinv,
@@ -1042,17 +1022,8 @@ def bn_relu_backward_pooled2(y: NHWC, gy: NHWC, idx, gskip: NHWC, skip_mode: int
                              sync=None):
     """bn_relu_backward_pooled with the dual-task second skip gradient (skip_mode 2: gskip2 = the semantic decoder's
     [t2; t1] skip gradient, added to the -/+ difference gradient before the pooled term)."""
-    if frozen or sync is not None:
-        return _bn_backward_desc(
-            frozen, sync, BN_BWD_POOLED2, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias,
-            dy, ws, dy_bound, gy=gy, idx=_ptr(idx), gskip=gskip, skip_mode=skip_mode,
-            gskip2=gskip2)
-    _check(
-        lib().scd_bn_relu_backward_pooled2(y, gy, _ptr(idx), gskip, skip_mode, gskip2, nseg, smean.data_ptr(),
-                                           sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), shift.data_ptr(),
-                                           _ptr(dgamma), _ptr(dbeta), _ptr(dbias), dy, _ptr(dy_bound), ws.data_ptr(),
-                                           ws.numel(), _stream()),
-        "scd_bn_relu_backward_pooled2")
+    bn_backward(BN_BWD_POOLED2, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws, dy_bound,
+                frozen=frozen, sync=sync, gy=gy, idx=idx, gskip=gskip, skip_mode=skip_mode, gskip2=gskip2)
 
 
 def bn_head_workspace_bytes(n, h, w, c, nseg, n_out) -> int:
@@ -1065,31 +1036,15 @@ def bn_relu_backward_head(y: NHWC, gout: torch.Tensor, w_head: torch.Tensor, n_o
     """bn_relu_backward of da = gout . w_head, the 1x1 head's input gradient (conv1x1_bwd's gx, never materialised);
     gout NCHW [n][n_out][h][w], w_head [n_out][C].  `w_grad` ([n_out][C]): also the head's weight grad from the same
     pass (workspace bn_head_workspace_bytes)."""
-    if frozen or sync is not None:
-        return _bn_backward_desc(
-            frozen, sync, BN_BWD_HEAD, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-            ws, dy_bound, gout=gout.data_ptr(), w_head=w_head.data_ptr(), n_out=n_out,
-            w_grad=_ptr(w_grad))
-    _check(
-        lib().scd_bn_relu_backward_head(y, gout.data_ptr(), w_head.data_ptr(), n_out, nseg, smean.data_ptr(),
-                                        sinv.data_ptr(), _ptr(gamma), scale.data_ptr(), shift.data_ptr(), _ptr(dgamma),
-                                        _ptr(dbeta), _ptr(dbias), dy, _ptr(dy_bound), _ptr(w_grad), ws.data_ptr(),
-                                        ws.numel(), _stream()),
-        "scd_bn_relu_backward_head")
+    bn_backward(BN_BWD_HEAD, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws, dy_bound,
+                frozen=frozen, sync=sync, gout=gout, w_head=w_head, n_out=n_out, w_grad=w_grad)
 
 
 def bn_relu_backward_tiles(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, tile_rec, ntiles, dgamma, dbeta,
                            dbias, dy: NHWC, ws, dy_bound=None, frozen=False, sync=None):
     """bn_relu_backward with the partial sums from conv-epilogue tile records (conv_igemm(..., bn_bwd=...))."""
-    if frozen or sync is not None:
-        return _bn_backward_desc(
-            frozen, sync, BN_BWD_TILES, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy,
-            ws, dy_bound, da=da, tile_rec=tile_rec.data_ptr(), ntiles=ntiles)
-    _check(
-        lib().scd_bn_relu_backward_tiles(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
-                                         shift.data_ptr(), tile_rec.data_ptr(), ntiles, _ptr(dgamma), _ptr(dbeta),
-                                         _ptr(dbias), dy, _ptr(dy_bound), ws.data_ptr(), ws.numel(), _stream()),
-        "scd_bn_relu_backward_tiles")
+    bn_backward(BN_BWD_TILES, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, dy, ws, dy_bound,
+                frozen=frozen, sync=sync, da=da, tile_rec=tile_rec, ntiles=ntiles)
 
 
 def bn_relu_backward_coef(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, shift, tile_rec, ntiles, coef, dgamma,
@@ -1098,17 +1053,8 @@ def bn_relu_backward_coef(y: NHWC, da: NHWC, nseg, smean, sinv, gamma, scale, sh
     sums) for a consumer that forms dy itself (wgrad_plan(..., rows_bn=...)).  tile_rec None: a pass over (y, da).
     `dy_bound` (with `da_bound`, a bound of |da|): raised to a bound of |dy| from the statistics (the h2 rows bound of
     that consumer)."""
-    if frozen or sync is not None:
-        return _bn_backward_desc(
-            frozen, sync, BN_BWD_COEF, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, None,
-            ws, dy_bound, da=da, tile_rec=_ptr(tile_rec), ntiles=ntiles, coef=coef.data_ptr(),
-            da_bound=_ptr(da_bound))
-    _check(
-        lib().scd_bn_relu_backward_coef(y, da, nseg, smean.data_ptr(), sinv.data_ptr(), _ptr(gamma), scale.data_ptr(),
-                                        shift.data_ptr(), _ptr(tile_rec), ntiles, coef.data_ptr(), _ptr(dgamma),
-                                        _ptr(dbeta), _ptr(dbias), _ptr(da_bound), _ptr(dy_bound), ws.data_ptr(),
-                                        ws.numel(), _stream()),
-        "scd_bn_relu_backward_coef")
+    bn_backward(BN_BWD_COEF, y, nseg, smean, sinv, gamma, scale, shift, dgamma, dbeta, dbias, None, ws, dy_bound,
+                frozen=frozen, sync=sync, da=da, tile_rec=tile_rec, ntiles=ntiles, coef=coef, da_bound=da_bound)
 
 
 def channel_sum(x: NHWC, out: torch.Tensor, ws: torch.Tensor):
